@@ -18,6 +18,13 @@ select the other north-star configs.  Random-init weights, synthetic token batch
 (no network); every timed step is a full forward + backward + gradient all-reduce +
 AdamW update.  W untimed warmup steps, then exactly K steps bracketed by barrier +
 device synchronize; the time is the MAX over ranks; rank 0 prints one JSON line.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.
+``--dump-outputs DIR`` also writes, after the timed steps, what the last one computed (the loss
+and the parameters it left) as ``DIR/*.npy``; the weights and the token batches are seeded, so two
+builds run with the same arguments can be compared file by file.  ``--full`` is where any
+measurement beyond the headline figure belongs; today there is none, the other studies are
+separate tools (``bench/``, ``scripts/``).
 """
 from __future__ import annotations
 
@@ -85,6 +92,30 @@ def _launch_ranks(n: int) -> int:
     return r.returncode if r.returncode > 0 else (1 if r.returncode else 0)
 
 
+DUMP_BUDGET_BYTES = 48 * 2**20  # --dump-outputs: all files together, float32
+
+
+def _dump_outputs(dirname: str, loss: float, state: dict) -> None:
+    """``--dump-outputs``: what a caller of the timed step holds after the last one -- the loss it
+    returned (``loss.npy``, float64, the mean over the ranks that see it) and the parameters it
+    left (``param.<state-dict key>.npy``, float32, flattened).  The budget is split evenly over
+    the tensors; a larger tensor is sampled at indices drawn from a generator seeded by the
+    tensor's position in the state dict, so two builds run with the same arguments write the same
+    elements."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loss.npy"), np.asarray([loss], dtype=np.float64))
+    cap = max(1, DUMP_BUDGET_BYTES // 4 // max(1, len(state)))
+    for i, (name, t) in enumerate(state.items()):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            g = torch.Generator(device="cpu").manual_seed(i)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(dirname, f"param.{name}.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -117,6 +148,13 @@ def main():
                     help="collective transport (default auto: the native RCCL communicator at N > 1); ipc = the "
                          "peer-access collectives of parallel/ipc_comm.py (DDP / FSDP)")
     ap.add_argument("--json", default=None, help="also write the result line to this file")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed -- its loss and "
+                         "the parameters it left -- as DIR/<name>.npy (float32; a seeded sample of large tensors)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure; there are none today (the "
+                         "kernel, baseline and scaling studies are separate tools under bench/ and scripts/), "
+                         "so the run is the plain one")
     a = ap.parse_args()
 
     env_ws = os.environ.get("WORLD_SIZE")
@@ -219,6 +257,11 @@ def main():
                         dtype=torch.float64, device=info.device)
     if info.world_size > 1:
         torch.distributed.all_reduce(peak, op=torch.distributed.ReduceOp.MAX)
+    if a.dump_outputs:
+        state = engine.full_state_dict()  # collective; the dict arrives on rank 0
+        if info.is_main:
+            _dump_outputs(a.dump_outputs, loss_v, state)
+        del state
     tokens_per_step = B * (S - 1) * engine.dp_world
     value = tokens_per_step * a.steps / dt
     n = info.world_size

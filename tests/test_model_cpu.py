@@ -314,48 +314,49 @@ def test_kv_cache_decode_matches_recompute(act):
 
 
 # ---------------------------------------------------------------- parity with the reference module
-_REF_GPT = "/root/reference/models/gpt.py"
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _reference_module():
-    """``/root/reference/models/gpt.py`` as shipped, with its two documented one-line crash
-    fixes applied in memory (``self.dim`` read before it is set,
-    ``:177-178``; undefined ``x`` in ``forward``, ``:227``)."""
-    import types
+def _golden(name):
+    """A fixture recorded from the reference's ``models/gpt.py`` as shipped, with its two
+    documented one-line crash fixes applied in memory (``self.dim`` read
+    before it is set, ``:177-178``; undefined ``x`` in ``forward``, ``:227``) -- see
+    ``tests/golden/README.md``."""
+    import numpy as np
 
-    if not os.path.exists(_REF_GPT):
-        pytest.skip("reference checkout not present")
-    pytest.importorskip("einops")
-    src = open(_REF_GPT).read()
-    for bad, good in (("nn.Embedding(vocab_size, self.dim)", "nn.Embedding(vocab_size, dim)"),
-                      ("nn.Embedding(max_position_embeddings, self.dim)", "nn.Embedding(max_position_embeddings, dim)"),
-                      ("x = self.embeddings(x, position_ids)", "x = self.embeddings(input_ids, position_ids)")):
-        assert src.count(bad) == 1, bad
-        src = src.replace(bad, good)
-    mod = types.ModuleType("reference_models_gpt")
-    exec(compile(src, _REF_GPT, "exec"), mod.__dict__)
-    return mod
+    with np.load(os.path.join(_GOLDEN, name)) as z:
+        return {k: torch.from_numpy(z[k]) for k in z.files}
+
+
+def _golden_state_dict(name):
+    """The reference module's ``state_dict()`` in its own key order."""
+    import json
+
+    z = _golden(name)
+    return {k: z[k] for k in json.loads(bytes(z["__keys__"].tolist()).decode())}
 
 
 def test_parity_with_reference_module():
-    """The reference's own TransformerDecoderLM (bugs fixed) vs ours: identical state-dict
-    keys and shapes, logits with and without a key-padding mask, and every parameter gradient
-    of the cross-entropy loss (fused path, manual backward)."""
-    ref_mod = _reference_module()
+    """The reference's own TransformerDecoderLM (bugs fixed; its state dict, logits and
+    gradients recorded in ``tests/golden/``) vs ours: identical state-dict keys and shapes,
+    logits with and without a key-padding mask, and every parameter gradient of the
+    cross-entropy loss (fused path, manual backward)."""
     D, hd, H, L, V, S = 64, 16, 4, 2, 97, 24
-    torch.manual_seed(0)
-    ref = ref_mod.TransformerDecoderLM(dim=D, head_dim=hd, heads=H, num_layers=L, vocab_size=V,
-                                       max_position_embeddings=S).eval()
     ours = TransformerDecoderLM(dim=D, head_dim=hd, heads=H, num_layers=L, vocab_size=V,
                                 max_position_embeddings=S)
-    rsd = ref.state_dict()
+    rsd = _golden_state_dict("ref_gpt_parity_state.npz")
+    exp = _golden("ref_gpt_parity_expected.npz")
     assert list(rsd) == list(ours.state_dict())
     assert all(rsd[k].shape == v.shape for k, v in ours.state_dict().items())
     ours.load_state_dict(rsd)
     for pad in (False, True):
         ids, pos, mask, tg = batch(pad=pad)
+        tag = "pad" if pad else "nopad"
+        # the recorded outputs belong to exactly these inputs
+        assert torch.equal(ids, exp[f"ids_{tag}"]) and torch.equal(tg, exp[f"targets_{tag}"])
+        assert mask is None or torch.equal(mask, exp[f"mask_{tag}"])
         with torch.no_grad():
-            want = ref(ids, pos, mask)
+            want = exp[f"logits_{tag}"]
             got = ours(ids, pos, mask)
         rows = ~mask if mask is not None else torch.ones(ids.shape, dtype=torch.bool)
         assert torch.allclose(got[rows], want[rows], atol=2e-5, rtol=1e-5), (got[rows] - want[rows]).abs().max()
@@ -364,11 +365,11 @@ def test_parity_with_reference_module():
     store = LocalStore(ours, "cpu")
     store.zero_grad()
     ours(ids, pos, mask, targets=tg).loss.backward()
-    logits = ref(ids, pos, mask)
-    F.cross_entropy(logits.reshape(-1, V), tg.reshape(-1), ignore_index=-100).backward()
     gp = dict(ours.named_parameters())
-    for n, p in ref.named_parameters():
-        err = (gp[n].grad - p.grad).norm() / p.grad.norm().clamp_min(1e-12)
+    assert {"grad." + n for n in gp} == {k for k in exp if k.startswith("grad.")}
+    for n, p in gp.items():
+        want = exp["grad." + n]
+        err = (p.grad - want).norm() / want.norm().clamp_min(1e-12)
         assert err < 1e-4, (n, err.item())
 
 
@@ -380,17 +381,15 @@ def test_reference_checkpoint_prefixes_round_trip(tmp_path, prefix):
     from distributed_pytorch_cookbook_amd.engine.data_parallel import DataParallelEngine
     from distributed_pytorch_cookbook_amd.utils.checkpoint import load_model_state, save_model_state
 
-    ref_mod = _reference_module()
-    torch.manual_seed(1)
-    ref = ref_mod.TransformerDecoderLM(dim=32, head_dim=16, heads=2, num_layers=2, vocab_size=97,
-                                       max_position_embeddings=24)
+    # the reference module's state dict (dim 32, head_dim 16, 2 heads, 2 layers, vocab 97, 24 positions)
+    ref_sd = _golden_state_dict("ref_gpt_checkpoint_state.npz")
     path = tmp_path / "ref.pt"
-    torch.save({prefix + k: v for k, v in ref.state_dict().items()}, path)
+    torch.save({prefix + k: v for k, v in ref_sd.items()}, path)
     eng = DataParallelEngine(tiny(D=32, H=2, hd=16), "cpu", lr=1e-3)
     eng.load_model_state(load_model_state(path))
     sd = eng.full_state_dict()
-    for k, v in ref.state_dict().items():
+    for k, v in ref_sd.items():
         assert torch.equal(sd[k], v), k
     out = save_model_state(sd, str(tmp_path / "ck"))
     back = torch.load(out, weights_only=True)
-    assert list(back) == list(ref.state_dict())
+    assert list(back) == list(ref_sd)
