@@ -249,18 +249,22 @@ __global__ __launch_bounds__(256) void ipc_coll_kernel(IpcCollArgs a) {
                                               : (n + IPC_ALIGN - 1) / IPC_ALIGN * IPC_ALIGN;
     const long long total = a.op == IPC_ALLREDUCE ? n : (long long)W * n;  // valid input elements
     const long long in_c = a.op == IPC_ALLREDUCE ? c : n;                  // input stride between shards
+    // valid elements of the shard that starts at input element b: all-reduce's last shards are cut
+    // by the end of the input; a reduce-scatter shard is its own n elements, never round64(n) (the
+    // elements past n belong to the next shard on the way in, and to nobody on the way out)
+    const auto shard_len = [&](long long b) { return a.op == IPC_ALLREDUCE ? min(c, total - b) : n; };
     // phase 0: this rank's input into its slot, shard by shard (sub-slice g of each)
     ipc_sub(c, g, lo, hi);
     for (int s = 0; s < W; ++s) {
       const long long b = (long long)s * in_c;  // first input element of shard s
-      const long long h = min(hi, max(lo, min(c, total - b)));
+      const long long h = min(hi, max(lo, shard_len(b)));
       if (h > lo) ipc_copy(a.in, b, false, mine, (long long)s * c, true, lo, h, bf);
     }
     ipc_barrier(a, g, 2 * e + 1);
     // phase 1: shard r summed over the ranks' slots (its valid part), kept in this rank's slot for
     // the second shot and written to the output
     const long long b = (long long)r * in_c;
-    const long long h = min(hi, max(lo, min(c, total - b)));
+    const long long h = min(hi, max(lo, shard_len(b)));
     if (h > lo) {
       // (all-reduce: the sum overwrites this rank's own copy of shard r, which no peer reads in
       // this phase -- each reads only its own shard -- and which the peers copy in phase 2)

@@ -207,6 +207,70 @@ def ipc_collectives_worker(rank, world, out):
         torch.save({"checked": checked}, out)
 
 
+def ipc_guard_worker(rank, world, out):
+    """Every collective into guarded views (tests/kernel_checks.py): the results exact against the
+    rank-order f32 sums and not one element written outside the output on any rank -- sizes that
+    are no multiple of the 64-element shard granule, the chunked path with a ragged last chunk,
+    16-B aligned views and views one element off.  Reduce-scatter's input is guarded as well.
+    Every rank runs every collective whatever it finds (a rank that stopped early would leave its
+    peers waiting) and reports at the end."""
+    _init()
+    from kernel_checks import guard_touched, guarded
+    from distributed_pytorch_cookbook_amd.parallel import ipc_comm
+    from distributed_pytorch_cookbook_amd.parallel.ipc_comm import IpcComm
+
+    c = IpcComm(slot_mb=0.25, spin_limit=1 << 22)
+    W = world
+    failures = []
+    checked = 0
+
+    def verify(what, view, expect, *more_guards):
+        nonlocal checked
+        checked += 1
+        if not torch.equal(view, expect):
+            failures.append(f"{what}: wrong result")
+        for name, v in (("out", view),) + tuple(("in", g) for g in more_guards):
+            idx = guard_touched(v)
+            if idx.numel():
+                failures.append(f"{what}: {idx.numel()} guard elements of {name} written, offsets "
+                                f"{int(idx[0])}..{int(idx[-1])} relative to its {v.numel()} elements")
+
+    for dtype in (torch.float32, torch.bfloat16):
+        es = 4 if dtype == torch.float32 else 2
+        for off in (False, True):
+            def gv(n, fill=None):
+                return guarded(n, dtype, "cuda", offset=off, fill=fill)
+
+            for n in (1, 63, 65, 1000, c._cap(ipc_comm.REDUCE_SCATTER, es) + 37):
+                full = [_ipc_input(p, W * n, dtype, 1) for p in range(W)]
+                inp, outp = gv(W * n, full[rank]), gv(n)
+                c.reduce_scatter(outp, inp)
+                exp = sum(f.float() for f in full).to(dtype)[rank * n:(rank + 1) * n]
+                verify(f"reduce_scatter {dtype} n={n} offset={off} rank={rank}", outp, exp, inp)
+            for n in (1, 63, 65, 1000, c._cap(ipc_comm.ALLGATHER, es) + 37):
+                gath = gv(W * n)
+                c.all_gather(gath, _ipc_input(rank, n, dtype, 2))
+                verify(f"all_gather {dtype} n={n} offset={off} rank={rank}", gath,
+                       torch.cat([_ipc_input(p, n, dtype, 2) for p in range(W)]))
+            for n in (1, 63, 65, 1000, c._cap(ipc_comm.BROADCAST, es) + 37):
+                b = gv(n, _ipc_input(rank, n, dtype, 3))
+                c.broadcast(b, src=W - 1)
+                verify(f"broadcast {dtype} n={n} offset={off} rank={rank}", b, _ipc_input(W - 1, n, dtype, 3))
+            for n in (1, 63, 65, 1000, c._cap(ipc_comm.ALLREDUCE, es) + 37):
+                t = gv(n, _ipc_input(rank, n, dtype, 4))
+                c.all_reduce(t)
+                acc = torch.zeros(n, device="cuda")
+                for p in range(W):
+                    acc = acc + _ipc_input(p, n, dtype, 4).float()
+                verify(f"all_reduce {dtype} n={n} offset={off} rank={rank}", t, acc.to(dtype))
+    torch.cuda.synchronize()
+    c.check()
+    c.destroy()
+    assert not failures, "\n".join(failures)
+    if rank == 0:
+        torch.save({"checked": checked}, out)
+
+
 def ipc_engine_worker(rank, world, out, kind, steps, graph):
     """DDP / FSDP over the peer-access transport, two ranks on cuda:0, the step captured into a
     HIP graph on both ranks when ``graph``: the N > 1 capture path (collective capture decision,

@@ -18,6 +18,17 @@ def test_ipc_collectives_ranks_share_one_gpu(tmp_path, world):
     assert torch.load(out, weights_only=True)["checked"] == 48 + 2 + 6 + 1 + 1 + 10
 
 
+@pytest.mark.parametrize("world", [2, 4])
+def test_ipc_collectives_stay_inside_their_buffers(tmp_path, world):
+    """Guard bands around every output (and reduce-scatter's input): 2 dtypes x aligned / one
+    element off x 5 sizes x 4 collectives, exact results, no element written outside."""
+    from dist_workers_gpu import ipc_guard_worker
+
+    out = tmp_path / "ipc_guard.pt"
+    run_workers(ipc_guard_worker, world, str(out), timeout=110)
+    assert torch.load(out, weights_only=True)["checked"] == 2 * 2 * 5 * 4
+
+
 @pytest.fixture(scope="module")
 def ref():
     return reference_state(steps=3)
