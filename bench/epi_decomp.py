@@ -90,13 +90,8 @@ def main():
         cases = [c for c in cases if c[0].split("@")[0] in a.only]
     fns = {}
     for name, impl, fn in cases:
-        # impl: forced implementation (-1 = table), or (impl, {lab variant key: value})
-        impl, var = impl if isinstance(impl, tuple) else (impl, {})
-
-        def run(impl=impl, fn=fn, var=var):
+        def run(impl=impl, fn=fn):  # impl: forced implementation (-1 = table)
             _lib.set_gemm_impl(impl)
-            for k in range(2):
-                _lib.set_gemm_variant(k, var.get(k, -1))
             fn()
         run()
         torch.cuda.synchronize()
@@ -106,8 +101,6 @@ def main():
         for k, fn in fns.items():
             times[k].append(time_ms(fn, a.iters))
     _lib.set_gemm_impl(-1)
-    for k in range(2):
-        _lib.set_gemm_variant(k, -1)
     fl = 2.0 * T * 4 * D * D
     rows = []
     for k, v in times.items():

@@ -244,8 +244,8 @@ def lib() -> ctypes.CDLL:
                 fn.restype = c_int
             handle.dpc_gemm_set_impl.argtypes = [c_int]
             handle.dpc_gemm_set_impl.restype = None
-            handle.dpc_gemm_set_variant.argtypes = [c_int, c_int]
-            handle.dpc_gemm_set_variant.restype = None
+            handle.dpc_gemm_explain.argtypes = [ctypes.POINTER(GemmArgs), ctypes.c_char_p, c_int]
+            handle.dpc_gemm_explain.restype = c_int
             handle.dpc_gemm_last_kernel.argtypes = []
             handle.dpc_gemm_last_kernel.restype = c_int
             handle.dpc_gemm_set_xcd_split.argtypes = [c_int]
@@ -279,9 +279,8 @@ forced_gemm_impl = -1
 
 
 def set_gemm_impl(impl: int) -> None:
-    """Force a GEMM implementation (tests / sweeps): -1 auto (default), 1 register-staged v1,
-    2-4 LDS-DMA 128x128 v2 variants, 10 the 256x128 v3, 16-26 the persistent 256x256 v7 / v8 / v9
-    placements (table at the dispatcher, ``csrc/gemm.hip``)."""
+    """Force a GEMM implementation (tests / sweeps): -1 auto (default), else an id of the
+    implementation table (``csrc/gemm_plan.h:GEMM_IMPLS``)."""
     global forced_gemm_impl
     forced_gemm_impl = int(impl)
     lib().dpc_gemm_set_impl(int(impl))
@@ -293,10 +292,13 @@ def gemm_last_kernel() -> int:
     return int(lib().dpc_gemm_last_kernel())
 
 
-def set_gemm_variant(key: int, value: int) -> None:
-    """Lab switch for same-process A/Bs of one kernel's variants (``gemm7.hip:g_variant``):
-    key 0 = v9 EPI 1 store layout (1: the round-4 half-line form); -1 = default."""
-    lib().dpc_gemm_set_variant(int(key), int(value))
+def gemm_explain(args: GemmArgs) -> str:
+    """The dispatcher's plan for ``args`` as one line of text (``csrc/gemm_plan.h:gemm_plan_text``:
+    steps, kernel instantiation, grid, split-K plan; it ends in ``last=<gemm_last_kernel() code>``).
+    Launches nothing."""
+    buf = ctypes.create_string_buffer(1024)
+    lib().dpc_gemm_explain(ctypes.byref(args), buf, len(buf))
+    return buf.value.decode()
 
 
 def set_gemm_splits(n: int) -> None:

@@ -3,54 +3,9 @@
 // and the LDS-DMA (buffer_load ... lds) tile issue.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"  // GemmArgs
 
 namespace dpc {
-
-struct GemmArgs {
-  const void* A;
-  const void* B;
-  void* C;
-  const float* bias;      // [N] f32, optional
-  const float* residual;  // [M][ldr] f32, optional (may alias C)
-  const void* aux_in;     // [M][ld_aux_in] bf16, optional: multiply by act'(aux_in)
-  void* aux_out;          // [M][ld_aux_out] bf16, optional: store pre-activation
-  const float* alpha_ptr; // device scalar multiplier, optional
-  float* colsum;          // [N] f32, optional: colsum[n] += sum_m v (v after act_bwd, before act)
-  long long lda, ldb, ldc, ldr, ld_aux_in, ld_aux_out;
-  int M, N, K;
-  float alpha;
-  int act;         // activation applied after bias (Act)
-  int act_bwd;     // multiply by act'(aux_in) (Act)
-  int out_f32;     // C is f32 (else bf16)
-  int accumulate;  // C += result (f32 output only)
-  int a_kmaj, b_kmaj;
-  // stored extents of the operands ([rows][cols] as laid out in memory); reads beyond them
-  // return zeros.  k-major: rows = M or N, cols = K;  mn-major: rows = K, cols = M or N.
-  int a_r, a_c, b_r, b_c;
-  // set by the dispatcher (callers pass 0): > 1 = XCD-aligned split-K into this many k-ranges
-  int ksplit;
-  // caller's implementation choice (0 = the dispatcher's shape policy), e.g. from the
-  // measured per-shape table of ops/gemm.py (autotuned on MI355X); a forced global impl
-  // (dpc_gemm_set_impl, sweeps / tests) takes precedence
-  int impl;
-  // gemm_f32.hip only: aux_in / aux_out are f32 (else bf16)
-  int aux_f32;
-  // split-K workspace (optional, f32, ws_bytes long): the v7 kernel stores each k-range's
-  // partial tile there with plain stores and a reduction pass sums them into C, instead of
-  // f32 atomics into C (gemm7.hip: dpc_gemm7)
-  void* ws;
-  long long ws_bytes;
-  // set by the dispatcher (callers pass 0): epilogue stores with the non-temporal bit -- bit 0 the
-  // bf16 C / aux_out stores, bit 1 the f32 C stores (DPC_GEMM_NT, default 3).  The short-K
-  // forward products spent 20-35 % of their time in the tile-end store burst; with nt stores
-  // v9 runs the GPT-2 QKV / up / LM-head forward 947 / 964 / 1031 -> 1151 / 1150 / 1163 TF/s
-  // and 8192^3 1327 -> 1448 (bench/g7lab epi set, profiles/r4_gemm/lab_epi_nt.log)
-  int nt_store;
-  // forward epilogues with aux_out and act == ACT_GELU: aux_out = bf16(act'(v)) instead of the
-  // pre-activation bf16(v), for an input gradient with act_bwd = ACT_MUL (models/fused.py: the
-  // FFN up-projection)
-  int aux_deriv;
-};
 
 // 16-B epilogue stores, plain or non-temporal (GemmArgs::nt_store; the flag is a kernel
 // argument, so the branch is wave-uniform)

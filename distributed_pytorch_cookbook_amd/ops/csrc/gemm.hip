@@ -21,7 +21,12 @@
 //     CDNA4 transposing LDS read, which yields the k-run per lane that MFMA wants.
 //   * workgroup ids are remapped so consecutive tiles share an XCD (private L2), then
 //     walked in GROUP_M-row supertiles for operand reuse.
-#include "gemm.h"
+#include "gemm9_kern.h"
+// the persistent kernels' instantiations are compiled in gemm7_part*.hip (ops/gen_gemm_parts.py)
+#define G7_SIG (dpc::GemmArgs, unsigned long long, unsigned long long, dpc::G7Plan)
+#define G7_INST(F, K, ...) extern template __global__ void dpc::K<__VA_ARGS__> G7_SIG;
+#include "gemm7_extern.inc"
+#undef G7_INST
 
 #include <cstdio>
 #include <cstdlib>
@@ -631,223 +636,166 @@ __global__ __launch_bounds__((V3Cfg<BM_, BN_, WM, WN, KB, STAGES>::NTH), (V3Cfg<
 
 using namespace dpc;
 
-template <int BM_, int BN_, int WM, int WN, int KB, int STAGES>
-static void launch_v3(const GemmArgs* a, dim3 grid, hipStream_t stream, unsigned long long ab,
-                      unsigned long long bb) {
-  constexpr int NTH = V3Cfg<BM_, BN_, WM, WN, KB, STAGES>::NTH;
-  if (a->a_kmaj && a->b_kmaj)
-    hipLaunchKernelGGL((gemm3_kernel<BM_, BN_, WM, WN, KB, STAGES, true, true>), grid, dim3(NTH), 0, stream, *a, ab, bb);
-  else if (a->a_kmaj)
-    hipLaunchKernelGGL((gemm3_kernel<BM_, BN_, WM, WN, KB, STAGES, true, false>), grid, dim3(NTH), 0, stream, *a, ab, bb);
-  else if (!a->b_kmaj)
-    hipLaunchKernelGGL((gemm3_kernel<BM_, BN_, WM, WN, KB, STAGES, false, false>), grid, dim3(NTH), 0, stream, *a, ab, bb);
-  else
-    hipLaunchKernelGGL((gemm3_kernel<BM_, BN_, WM, WN, KB, STAGES, false, true>), grid, dim3(NTH), 0, stream, *a, ab, bb);
+// ---- the dispatcher.  gemm_plan.h decides (which implementation, kernel instantiation, grid,
+// split-K plan, reduction passes: a pure function, pinned on the CPU by
+// tests/test_gemm_plan_cpu.py); gemm_run below launches what a plan says and decides nothing.
+//
+// The persistent family (v7 / v8 / v7d: gemm7_kern.h, v9: gemm9_kern.h) -- why its shape
+// (MI355X, measured with bench/gemm_ab.py): the 8-wave ping-pong kernels it replaced paid two
+// workgroup barriers per 16 MFMAs and re-read 12 fragments per 32 MFMAs; on short-K products
+// (K = 768: the QKV / out / up / LM-head forward products of GPT-2 small) they also drained the
+// whole pipeline at every tile -- prologue latency + a 128 KiB store burst per CU with the matrix
+// pipe idle -- and ran at ~680 TF/s against hipBLASLt's ~1,200.  Here:
+//   * each wave owns a 128x128 output tile: 8 x 8 accumulators of v_mfma_f32_16x16x32_bf16
+//     (256 accumulator registers; a 512-register wave, one per SIMD), i.e. 16 fragment reads
+//     per 64 MFMAs (0.25 / MFMA vs 0.375) and ONE workgroup barrier per 32-deep k-slice
+//     (1,024 MFMA cycles per SIMD);
+//   * the k-slices of all the tiles a workgroup owns form one stream: an NS-slot LDS ring
+//     (32 KiB per slot: A 256x32 + B 256x32) filled by LDS-DMA (buffer_load ... lds) DIST =
+//     NS-1 slices ahead, never drained at a tile boundary, so the next tile's first slices are
+//     in flight while the previous tile's epilogue runs;
+//   * fragments of slice q+1 are read into a second register set while the MFMAs of slice q
+//     run (two named sets, the loop unrolled by two);
+//   * the MFMA operands are swapped (C^T = B A^T): lane l of a 16x16 accumulator holds output
+//     row l & 15 and four CONSECUTIVE columns 4 (l >> 4) + r, so the epilogue works straight
+//     from registers -- no LDS staging, no barrier: 16-B f32 stores, and for bf16 outputs
+//     v_permlane16_swap pairs two fragments' 8-B halves into one 16-B store per lane.
+// LDS images and fragment reads are the v3 ones (gemm.h): k-major [rows][32] with the 16-B
+// chunk swizzle, mn-major [k][128-column halves] read with ds_read_b64_tr_b16.
+//
+// Synchronisation (per slice q, every wave):  body(q) = MFMAs on frags(q) | reads of frags(q+1)
+// from slot (q+1) % NS | DMA of slice q+DIST into slot (q+DIST) % NS | epilogue if q ends a
+// tile;  then vmcnt(slice q+2 landed) + s_barrier.
+//   RAW: slot (q+2) is read in body(q+1), after this barrier, which every wave enters after its
+//        own counted vmcnt for slice q+2 (its DMA pieces are older than the count).
+//   WAR: slot (q+DIST) % NS held slice q-1, read in body(q-2) and consumed by the MFMAs of
+//        body(q-1), i.e. retired before every wave passed barrier(q-1) -- before any wave
+//        can be in body(q).
+static_assert(GP_ACT_GELU == ACT_GELU && GP_ACT_MUL == ACT_MUL && GP_G7_KB == G7_KB && G_SP_DEFAULT == 3,
+              "gemm_plan.h's copies of the kernels' constants");
+
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
-static inline long long operand_bytes(long long rows, long long cols, long long ld) {
-  // bytes a tile load may legitimately touch: [rows][ld], 16-B chunks up to roundup8(cols)
-  if (rows <= 0 || cols <= 0) return 0;
-  return ((rows - 1) * ld + ((cols + 7) / 8) * 8) * 2;
-}
-
-template <int KB, int STAGES>
-static void launch_v2(const GemmArgs* a, dim3 grid, hipStream_t stream, unsigned long long ab,
-                      unsigned long long bb) {
-  if (a->a_kmaj && a->b_kmaj) hipLaunchKernelGGL((gemm2_kernel<KB, STAGES, true, true>), grid, dim3(NT), 0, stream, *a, ab, bb);
-  else if (a->a_kmaj) hipLaunchKernelGGL((gemm2_kernel<KB, STAGES, true, false>), grid, dim3(NT), 0, stream, *a, ab, bb);
-  else if (!a->b_kmaj) hipLaunchKernelGGL((gemm2_kernel<KB, STAGES, false, false>), grid, dim3(NT), 0, stream, *a, ab, bb);
-  else hipLaunchKernelGGL((gemm2_kernel<KB, STAGES, false, true>), grid, dim3(NT), 0, stream, *a, ab, bb);
-}
-
-// -1: auto; 1: v1; 2: v2 KB64 x2 stages; 3: KB64 x3; 4: KB32 x3; 5: KB32 x4;
-// 6-10: v3 (6: 256x256 KB64 x2, 7: 256x256 KB32 x4, 8: 256x128 KB64 x2, 9: 256x128 KB32 x4,
-// 10: 256x128 KB32 x3); (11-14: v4 / v5 / v6, removed);
-// 16 / 19 / 20: v7 (gemm7.hip: persistent one-wave-per-SIMD 256x256, 5-slot ring; DMA
-// placement 0 / 1 / 2); 17: v7, one unit per workgroup; plain f32 products split K
-static int g_gemm_impl = -1;
-// XCD-aligned split-K mapping (tile_slot): measured ~6 % slower than the default mapping on
-// the GPT-2 weight gradients, so off unless requested (sweeps)
-static int g_xcd_split = 0;
-// > 0: force this split-K count for plain f32 products (sweeps)
-static int g_force_splits = 0;
-
-DPC_API void dpc_gemm_set_impl(int impl) { g_gemm_impl = impl; }
-DPC_API void dpc_gemm_set_xcd_split(int on) { g_xcd_split = on; }
-DPC_API void dpc_gemm_set_splits(int s) { g_force_splits = s; }
-
-static inline bool al(const void* p, int b) { return ((uintptr_t)p % b) == 0; }
-
-// Per-class implementation override for sweeps, from the environment, e.g.
-// DPC_GEMM_POLICY="fs=11,dl=4": fs / fl = forward (both k-major) with K <= / > 1024,
-// ds / dl = dgrad (B mn-major) with K <= / > 2304, w = weight gradient (both mn-major).
-static int g_policy[5] = {0, 0, 0, 0, 0};
-static int g_policy_read = 0;
-static int policy_impl(const GemmArgs* a) {
-  if (!g_policy_read) {
-    g_policy_read = 1;
+// The process-wide settings: the environment is read here, once; the setters below write to it.
+static GemmSettings& settings() {
+  static GemmSettings g = [] {
+    GemmSettings s;
     if (const char* e = getenv("DPC_GEMM_POLICY")) {
       const char* names[5] = {"fs", "fl", "ds", "dl", "w"};
       for (int c = 0; c < 5; ++c) {
         char key[8];
         snprintf(key, sizeof key, "%s=", names[c]);
         for (const char* q = e; (q = strstr(q, key)) != nullptr; ++q)
-          if (q == e || q[-1] == ',') { g_policy[c] = atoi(q + strlen(key)); break; }
+          if (q == e || q[-1] == ',') { s.policy[c] = atoi(q + strlen(key)); break; }
       }
     }
-  }
-  int c;
-  if (a->a_kmaj && a->b_kmaj) c = a->K <= 1024 ? 0 : 1;
-  else if (a->a_kmaj) c = a->K <= 2304 ? 2 : 3;
-  else if (!a->b_kmaj) c = 4;
-  else return 0;
-  return g_policy[c];
+    s.nt_store = env_int("DPC_GEMM_NT", s.nt_store);
+    s.act_lds_env = env_int("DPC_G7_ACTLDS", 1);
+    s.res_lds_env = env_int("DPC_G7_RESLDS", 1);
+    s.debug = env_int("DPC_G7_DEBUG", 0);
+    s.cus = 0;  // asked of the device by the first product (settings_for_launch)
+    return s;
+  }();
+  return g;
 }
 
-extern "C" int dpc_gemm7(const GemmArgs* a, int persistent, int sched, int splits, hipStream_t stream, int wn);
-extern "C" int dpc_gemm7_ok(const GemmArgs* a);
+static const GemmSettings& settings_for_launch() {
+  GemmSettings& s = settings();
+  if (s.cus <= 0) {
+    int dev = 0, n = 0;
+    const bool ok = hipGetDevice(&dev) == hipSuccess &&
+                    hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0;
+    s.cus = ok ? n : 256;
+  }
+  return s;
+}
 
-// GemmArgs::nt_store for every product (DPC_GEMM_NT: bit 0 bf16 outputs, bit 1 f32 outputs
-// non-temporal; bits 2-3 the cache scope of the v7 / v9 epilogue stores: 0 none, 1 sc0, 2 sc1,
-// 3 sc0 sc1).  Default 15 = nt + sc0 sc1: the epilogue's stores retire sooner, and the next
-// tile's counted DMA waits -- which CDNA4's one in-order vmcnt makes wait for them too -- stall
-// less.  Same box against nt alone (round 5, profiles/r5_epi/store_policy.log): up-projection
-// fused 402 -> 384 us, down-projection fused 367 -> 349, plain up 283 -> 274, plain input
-// gradient 300 -> 290; DDP 960.8K -> 971.6K (two runs each).  Bits 4-6: a separate scope for
-// the f32 outputs (gemm.h:g_f32_pol) -- default 77 = the above for bf16 outputs, PLAIN stores for
-// the f32 ones (the residual stream and the split-K slabs, which the next LayerNorm / the slab
-// reduction read back at once from the Infinity Cache): DDP +0.45 % same box, three interleaved
-// rounds (984.1 / 981.2 / 981.7K -> 989.7 / 984.5 / 985.5K, profiles/r5_epi/f32_store_scope.log).
-static int gemm_nt_mode() {
-  static int mode = -1;
-  if (mode < 0) mode = getenv("DPC_GEMM_NT") ? atoi(getenv("DPC_GEMM_NT")) : 77;
-  return mode;
+DPC_API void dpc_gemm_set_impl(int impl) { settings().impl = impl; }
+DPC_API void dpc_gemm_set_xcd_split(int on) { settings().xcd_split = on; }
+DPC_API void dpc_gemm_set_splits(int s) { settings().force_splits = s; }
+DPC_API void dpc_gemm7_set_act_lds(int v) { settings().act_lds = v; }  // -1: DPC_G7_ACTLDS; 0 / 1 forced
+DPC_API void dpc_gemm7_set_res_lds(int v) { settings().res_lds = v; }  // -1: DPC_G7_RESLDS; 0 / 1 forced
+DPC_API void dpc_set_cu_reserve(int r) { settings().cu_reserve = r < 0 ? 0 : r; }
+DPC_API int dpc_get_cu_reserve() { return settings().cu_reserve; }
+
+// GemmPlan::last_kernel of the last product launched (tests assert that a forced implementation
+// really ran instead of falling back)
+static int g_last_kernel = 0;
+DPC_API int dpc_gemm_last_kernel() { return g_last_kernel; }
+
+// kernel identity of a plan -> its instantiation; nullptr: not compiled in any part
+typedef void(*G7KernelFn) G7_SIG;
+static G7KernelFn g7_kernel_fn(const GemmKernelId& k) {
+  switch (gemm_kernel_key(k)) {
+#define G7_INST(F, K, ...) case gemm_kernel_key({F, {__VA_ARGS__}}): return K<__VA_ARGS__>;
+#include "gemm7_extern.inc"
+#undef G7_INST
+    default: return nullptr;
+  }
+}
+
+// K<..., AK, BK> for a runtime layout
+#define DPC_BY_LAYOUT(ak, bk, K, ...)                                                            \
+  ((ak) ? ((bk) ? K<__VA_ARGS__ true, true> : K<__VA_ARGS__ true, false>)                        \
+        : ((bk) ? K<__VA_ARGS__ false, true> : K<__VA_ARGS__ false, false>))
+
+// Launches the steps of a plan; the one place that maps a kernel identity to its instantiation
+// (the persistent families: g7_kernel_fn, from the generated list gemm7_extern.inc).
+static int gemm_run(const GemmPlan& p, const GemmArgs& a, hipStream_t stream) {
+  g_last_kernel = p.last_kernel;
+  if (p.rc != 0) return p.rc;
+  GemmArgs b = a;  // the dispatcher-owned fields
+  b.ksplit = p.ksplit;
+  b.nt_store = p.nt_store;
+  if (p.drop_ws) b.ws = nullptr;
+  const GemmKernelId& k = p.kernel;
+  const dim3 grid(p.grid), block(p.block);
+  for (int i = 0; i < p.nsteps; ++i) {
+    switch (p.steps[i]) {
+      case GS_CLEAR:
+        (void)hipMemset2DAsync(a.C, (size_t)a.ldc * 4, 0, (size_t)a.N * 4, (size_t)a.M, stream);
+        break;
+      case GS_SPLITK_REDUCE:
+        hipLaunchKernelGGL(g7_splitk_reduce, dim3(p.red_x), dim3(256), 0, stream, static_cast<float*>(a.C), a.ldc,
+                           static_cast<const float*>(a.ws), a.M, a.N, p.g7.splits, a.accumulate, p.nt_store & 2);
+        break;
+      case GS_COLSUM_REDUCE:
+        hipLaunchKernelGGL(g7_colsum_reduce, dim3(p.red_x, p.red_y), dim3(256), 0, stream, a.colsum,
+                           static_cast<const float*>(a.ws), 2 * p.g7.tiles_m, a.N);
+        break;
+      case GS_KERNEL:
+        if (k.family >= GK_V7) {
+          const G7KernelFn fn = g7_kernel_fn(k);
+          if (!fn) return (int)hipErrorInvalidDeviceFunction;  // not in gemm_parts.txt
+          hipLaunchKernelGGL(fn, grid, block, 0, stream, b, p.a_bytes, p.b_bytes, p.g7);
+        } else if (k.family == GK_V1) {
+          hipLaunchKernelGGL(DPC_BY_LAYOUT(k.t[0], k.t[1], gemm_kernel, ), grid, block, 0, stream, b);
+        } else {
+          void (*fn)(GemmArgs, unsigned long long, unsigned long long) = nullptr;
+          if (k.family == GK_V2 && k.t[0] == 64 && k.t[1] == 2) fn = DPC_BY_LAYOUT(k.t[2], k.t[3], gemm2_kernel, 64, 2, );
+          else if (k.family == GK_V2 && k.t[0] == 64 && k.t[1] == 3) fn = DPC_BY_LAYOUT(k.t[2], k.t[3], gemm2_kernel, 64, 3, );
+          else if (k.family == GK_V2 && k.t[0] == 32 && k.t[1] == 3) fn = DPC_BY_LAYOUT(k.t[2], k.t[3], gemm2_kernel, 32, 3, );
+          else if (k.family == GK_V3 && k.t[0] == 256 && k.t[1] == 128 && k.t[4] == 32 && k.t[5] == 3)
+            fn = DPC_BY_LAYOUT(k.t[6], k.t[7], gemm3_kernel, 256, 128, 4, 2, 32, 3, );
+          if (!fn) return (int)hipErrorInvalidDeviceFunction;
+          hipLaunchKernelGGL(fn, grid, block, 0, stream, b, p.a_bytes, p.b_bytes);
+        }
+        break;
+      default: break;
+    }
+  }
+  return (int)hipGetLastError();
 }
 
 DPC_API int dpc_gemm(const GemmArgs* a, hipStream_t stream) {
-  if (a->M <= 0 || a->N <= 0) return 0;
-  // aux_deriv: GELU' as the second output (v9 / v7 / v7-generic / v2 / v3 epilogues; v7d and the
-  // LDS-staged residual epilogue are skipped by gemm7.hip)
-  if (a->aux_deriv && (!a->aux_out || a->act != ACT_GELU)) return -1;
-  const int tiles = ((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN);
-  dim3 grid(tiles), block(NT);
-  // v2 requirements: a k-major operand must hold exactly K (% 64) columns (its k-tail is not
-  // zeroed by the descriptor), N % 4 == 0 and 16-B aligned f32 epilogue operands (vector
-  // epilogue), every operand inside a 31-bit byte range.
-  const long long ab = operand_bytes(a->a_r, a->a_c, a->lda);
-  const long long bb = operand_bytes(a->b_r, a->b_c, a->ldb);
-  const bool kmaj_ok = (!a->a_kmaj || (a->a_c == a->K && a->K % 64 == 0)) &&
-                       (!a->b_kmaj || (a->b_c == a->K && a->K % 64 == 0));
-  const bool v2_ok = kmaj_ok && a->N % 4 == 0 && ab > 0 && bb > 0 && a->K > 0 && a->ldc % 4 == 0 && a->ldr % 4 == 0 &&
-                     a->ld_aux_in % 4 == 0 && a->ld_aux_out % 4 == 0 &&
-                     al(a->C, a->out_f32 ? 16 : 8) && al(a->bias, 16) && al(a->residual, 16) &&
-                     al(a->aux_in, 8) && al(a->aux_out, 8) && al(a->colsum, 4);
-  int impl = g_gemm_impl;
-  if (impl < 0 && a->impl > 0) impl = a->impl;
-  const bool plain_any = !a->bias && !a->residual && !a->aux_in && !a->aux_out && !a->colsum && !a->act &&
-                         !a->act_bwd;
-  if (impl < 0 && plain_any && policy_impl(a) <= 0 && dpc_gemm7_ok(a)) {
-    // products without a fused epilogue -- the QKV / out / LM-head forward, every input
-    // gradient without act', the weight gradients (split K) -- run the persistent 4-wave
-    // kernel (v7); GPT-2 small B=64 shapes on MI355X: 940-1,220 TF/s vs 640-940 for the
-    // 8-wave / 128-wide kernels (bench/gemm_ab.py, profiles/r2_gemm/)
-    impl = 20;
-  }
-  // forward epilogues that read nothing per element (bias / activation / aux_out: the FFN
-  // products, whose table entries all name v9) default to v9's load-free epilogue when no table
-  // entry covers the shape -- e.g. the down projection as a bias-only product since round 6 (its
-  // residual add moved into the next LayerNorm), which the older policy sent to the 128 x 128
-  // kernel at 366 us against ~280
-  const bool fwd_epi = a->a_kmaj && a->b_kmaj && !plain_any && !a->residual && !a->accumulate && !a->aux_in &&
-                       !a->colsum && !a->act_bwd && a->K % 64 == 0 && a->K >= 192;
-  if (impl < 0 && fwd_epi && policy_impl(a) <= 0 && dpc_gemm7_ok(a)) impl = 26;
-  if (impl < 0) {
-    // Default per operand layout and depth, from the GPT-2 shape sweep on MI355X
-    // (bench/kernels.py, profiles/kernels_r1_*.json): forward products with a short K
-    // (<= 1024) are epilogue/prologue heavy and run best as 256x128 tiles two workgroups
-    // per CU (impl 10); deep or mn-major products keep the 128x128 2-stage kernel (impl 2),
-    // except dgrad at K <= 2304 and mid-size wgrad, where the 3-stage 32-deep ring wins.
-    impl = 1;
-    if (v2_ok) {
-      impl = 2;
-      if (a->a_kmaj && a->b_kmaj && a->K <= 1024) impl = 10;
-      else if (a->a_kmaj && !a->b_kmaj && a->K <= 1024) impl = 10;  // dgrad + act' / colsum epilogue
-      else if (a->a_kmaj && !a->b_kmaj && a->K <= 2304) impl = 4;
-      else if (!a->a_kmaj && !a->b_kmaj && a->M > 2304 && a->M <= 4096) impl = 4;
-      const int pol = policy_impl(a);
-      if (pol > 0) impl = pol;
-    }
-  }
-  // plain f32 products (weight gradients: small M x N, K = tokens) are split along K
-  const bool plain = a->out_f32 && !a->bias && !a->residual && !a->aux_in && !a->aux_out &&
-                     !a->colsum && !a->act && !a->act_bwd;
-  if (g_gemm_impl < 0 && a->impl <= 0 && v2_ok && plain && !a->a_kmaj && !a->b_kmaj && policy_impl(a) <= 0) {
-    // weight gradient: the split-K persistent kernel (v7, chosen above when its requirements
-    // hold -- its own planner splits K to fill the chip however few tiles there are), else the
-    // 2-stage 64-k kernel.  (Round 4: the pipeline stage proxy's micro-batch
-    // out-projection weight gradient, 1024 x 1024 x 16368, off the table, fell to the 2-stage
-    // kernel at 506 TF/s -- 8.7 ms of a 262 ms stage step, profiles/r4_pp/.)
-    if (impl != 20) impl = 2;
-  }
-  if (impl >= 15 && impl <= 26) {  // v7 (gemm7.hip): 4-wave 256x256, split-K f32 products
-    GemmArgs c = *a;
-    c.ksplit = 0;
-    c.nt_store = gemm_nt_mode();
-    // (25: the split DMA interleave forced for plain products, SCHED 6; 20 / 22 pick it for
-    // products with an mn-major operand; 26: v9, the 64-deep-stage kernel, which every other v7
-    // placement takes for plain nt products)
-    const int sched = impl == 19 ? 1 : (impl == 20 || impl == 17 || impl == 21 ? 2 : (impl == 22 ? 3 : (impl == 23 ? 4 : (impl == 24 ? 5 : (impl == 25 ? 6 : (impl == 26 ? 7 : 0))))));
-    // 21: v8 -- 256x128 tiles, two persistent workgroups per CU (epilogue beside MFMAs)
-    const int rc = dpc_gemm7(&c, impl != 17, sched, g_force_splits > 0 ? g_force_splits : 0, stream,
-                             impl == 21 ? 64 : 128);
-    if (rc >= 0) return rc;
-    impl = v2_ok ? 2 : 1;  // requirements not met: the 128x128 kernels
-  }
-  if (impl >= 2 && !v2_ok) impl = 1;
-  GemmArgs b = *a;  // dispatcher-owned copy: split-K mode is decided here
-  b.ksplit = 0;
-  b.nt_store = gemm_nt_mode();
-  if (impl >= 2) {
-    int bm = BM, bn = BN;
-    if (impl >= 6) {
-      bm = 256;  // (v3-v6)
-      bn = (impl == 8 || impl == 9 || impl == 10) ? 128 : 256;
-    }
-    const int t = ((a->M + bm - 1) / bm) * ((a->N + bn - 1) / bn);
-    const int nk = (a->K + BKT - 1) / BKT;
-    int splits = 1;
-    if (plain) {
-      // Split-K count from a cost model fitted to the GPT-2 weight-gradient sweep on MI355X
-      // (bench/wgrad_splits.py, profiles/r1_wgrad_splits.txt): time ~ rounds(s) / s + beta * s,
-      // rounds = ceil(tiles * s / resident workgroups) (wave quantisation of the grid) and
-      // beta * s the split-K partial-sum atomics relative to the K-proportional MFMA work.
-      // resident workgroups per launch round: 256 CUs x workgroups per CU (LDS-bound, V2Cfg::WGS)
-      const int slots = impl >= 6 || impl == 3 ? 256 : (impl == 4 ? 768 : 512);  // (v3-v6: 1 WG/CU)
-      const double beta = 0.0056 * 32768.0 / (double)a->K;
-      double best = 1e30;
-      for (int s = 1; s <= 16 && (s == 1 || nk / s >= 8); ++s) {
-        const long long rounds = ((long long)t * s + slots - 1) / slots;
-        const double cost = (double)rounds / s + beta * s;
-        if (cost < best - 1e-9) { best = cost; splits = s; }
-      }
-      if (g_force_splits > 0) splits = g_force_splits;
-    }
-    if (splits > 1 && !a->accumulate)
-      hipMemset2DAsync(a->C, (size_t)a->ldc * 4, 0, (size_t)a->N * 4, (size_t)a->M, stream);
-    dim3 g(t * splits);  // 1-D: tile_slot() maps block -> (split, tile)
-    b.ksplit = splits > 1 ? (g_xcd_split ? -splits : splits) : 0;
-    switch (impl) {
-      case 3: launch_v2<64, 3>(&b, g, stream, ab, bb); break;
-      case 4: launch_v2<32, 3>(&b, g, stream, ab, bb); break;
-      case 10: launch_v3<256, 128, 4, 2, 32, 3>(&b, g, stream, ab, bb); break;
-      case 2: launch_v2<64, 2>(&b, g, stream, ab, bb); break;
-      default: return 1;  // (5-9, 11-14: removed implementations, chosen by no table or policy)
-    }
-    return (int)hipGetLastError();
-  }
-  if (a->a_kmaj && a->b_kmaj) hipLaunchKernelGGL((gemm_kernel<true, true>), grid, block, 0, stream, b);
-  else if (a->a_kmaj && !a->b_kmaj) hipLaunchKernelGGL((gemm_kernel<true, false>), grid, block, 0, stream, b);
-  else if (!a->a_kmaj && !a->b_kmaj) hipLaunchKernelGGL((gemm_kernel<false, false>), grid, block, 0, stream, b);
-  else hipLaunchKernelGGL((gemm_kernel<false, true>), grid, block, 0, stream, b);
-  return (int)hipGetLastError();
+  return gemm_run(gemm_plan(*a, settings_for_launch()), *a, stream);
+}
+
+// The plan of a product as one line of text (gemm_plan.h: gemm_plan_text), ending in the
+// dpc_gemm_last_kernel() code the launch would leave; launches nothing.  Returns the length.
+DPC_API int dpc_gemm_explain(const GemmArgs* a, char* buf, int cap) {
+  return gemm_plan_text(gemm_plan(*a, settings_for_launch()), buf, cap);
 }

@@ -15,18 +15,6 @@ constexpr int G7_TA = 256 * G7_KB;     // bf16 elements per operand per slice (1
 constexpr int G7_SLOT = 2 * G7_TA;     // A + B
 constexpr int G7_NL = G7_TA / 512 / 4; // 1-KiB DMA pieces per wave per operand per slice (4)
 
-struct G7Plan {
-  int tiles_m, tiles_n;
-  int tile_n;  // tile width: 256 (v7) or 128 (v8)
-  int units;   // tiles x splits (split-major: unit = split * tiles + tile)
-  int grid;    // workgroups launched
-  int nk;      // k-slices per unit (even)
-  int nk_all;  // k-slices of the whole product (slices of a unit past it read zeros)
-  int splits;
-  int store_cnt;  // vector-memory ops the epilogue issues per wave-lane (0: unknown -> no credit)
-  int debug;      // experiments only (DPC_G7_DEBUG): 1 = no epilogue (main-loop ablations: ABL, bench/g7lab.hip)
-};
-
 // XCD-aware assignment: round i covers units [i*grid, (i+1)*grid); inside a round the blocks
 // that share an XCD (b % 8) get a contiguous run of unit ids (bijective for any grid), and unit
 // ids walk GROUP_M-row supertiles, so an XCD's concurrent tiles share A/B panels in its L2.

@@ -70,7 +70,7 @@ def forget_outstanding() -> None:
 
 # ---------------------------------------------------------------- resident-CU reserve
 # SURVEY.md §5.8 rule 4 (comm overlapped with compute on side streams): the persistent GEMMs
-# (ops/csrc/gemm7.hip) size their grid to occupy every CU, so an RCCL kernel resident on a
+# (ops/csrc/gemm_plan.h) size their grid to occupy every CU, so an RCCL kernel resident on a
 # CU while a GEMM launches would push that CU's GEMM workgroup -- and its whole share of the
 # tiles -- into a second round.  With DPC_CU_RESERVE=R, from the moment an asynchronous GPU
 # collective is enqueued until its handle is waited on, the GEMMs leave R CUs free for it

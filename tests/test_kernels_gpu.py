@@ -309,7 +309,7 @@ def test_gemm_v7_residual_epilogue_paths(res_lds, act, with_aux, with_bias, a_km
 @pytest.mark.parametrize("M,N,K", [(16000, 3072, 768), (12000, 2560, 1600), (10000, 2048, 576), (4096, 4352, 768),
                                    (65472, 3072, 768), (65472, 768, 3072), (9000, 1600, 2048)])
 def test_gemm_v7d_deferred_gelu_epilogues(M, N, K):
-    """impl 24 (gemm7.hip gemm7d_kernel): the FFN's GELU forward (bias + GELU + pre-activation,
+    """impl 24 (gemm7_kern.h gemm7d_kernel): the FFN's GELU forward (bias + GELU + pre-activation,
     both operands k-major) and GELU' input gradient (act'(aux_in) + column sums, B n-major)
     with the element-wise half deferred into the next tile's main loop.  Shapes give every
     persistent workgroup 1-3+ tiles (deferred steady state, the last-tile and ragged-M
@@ -378,6 +378,73 @@ def test_gemm_forced_split_k(impl, splits, M, N, K):
     ref = A.float().t() @ B.float()
     assert rel_err(acc - acc0, ref) < 2e-3
     assert rel_err(fresh, ref) < 2e-3
+
+
+_plan_refs = {}
+
+
+def _plan_ref(M, N, K):
+    """Operands and f32 references of test_gemm_plan_is_what_runs, computed once per shape."""
+    if (M, N, K) not in _plan_refs:
+        torch.manual_seed(11)
+        a = torch.randn(M, K, device=dev).bfloat16()
+        b = torch.randn(N, K, device=dev).bfloat16()
+        bias = torch.randn(N, device=dev)
+        z = torch.randn(M, N, device=dev).bfloat16()
+        r = {"a": a, "b": b, "bias": bias, "z": z, "plain": a.float() @ b.float().t()}
+        r["fwd"], r["fwd_aux"] = torch.empty(M, N, device=dev), torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+        _gemm_ref(a, b, True, True, r["fwd"], bias, 2, 0, None, r["fwd_aux"], None, 1.0, None, False)
+        r["dgrad"], r["dgrad_cs"] = torch.empty(M, N, device=dev), torch.zeros(N, device=dev)
+        _gemm_ref(a, b, True, True, r["dgrad"], None, 0, 2, z, None, None, 1.0, None, False, r["dgrad_cs"])
+        _plan_refs[(M, N, K)] = r
+    return _plan_refs[(M, N, K)]
+
+
+@pytest.mark.parametrize("impl", [-1, 2, 10, 20, 21, 26])
+@pytest.mark.parametrize("a_kmaj,b_kmaj", [(True, True), (True, False), (False, False)])  # nt / nn / tn
+@pytest.mark.parametrize("M,N,K", [(300, 264, 192), (257, 520, 1000)])
+def test_gemm_plan_is_what_runs(monkeypatch, impl, a_kmaj, b_kmaj, M, N, K):
+    """The plan the dispatcher explains (csrc/gemm_plan.h, pinned on the CPU by
+    test_gemm_plan_cpu.py) is what it launches: for the plain bf16 product, the f32 accumulate,
+    the bias + GELU + aux_out forward and the act' + column-sum input gradient, the kernel code
+    at the end of ``gemm_explain`` is ``gemm_last_kernel()`` after the call, and the results are
+    right.  The smallest shapes with a ragged second tile in M and N; K = 1000 fails the
+    persistent family's K % 32, so every id falls back there."""
+    r = _plan_ref(M, N, K)
+    A, B = _store(r["a"], a_kmaj), _store(r["b"], b_kmaj)
+    explained = []
+    call = _lib.call
+
+    def explain_then_call(name, args, device=None):
+        if name == "dpc_gemm":
+            explained.append(int(_lib.gemm_explain(args).rsplit("last=", 1)[1]))
+        call(name, args, device)
+        if name == "dpc_gemm":
+            explained.append(_lib.gemm_last_kernel())
+
+    monkeypatch.setattr(_lib, "call", explain_then_call)
+    acc0 = torch.randn(M, N, device=dev)
+    acc = acc0.clone()
+    aux = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+    cs = torch.zeros(N, device=dev)
+    _lib.set_gemm_impl(impl)
+    try:
+        ob = gemm(A, B, a_kmaj=a_kmaj, b_kmaj=b_kmaj)
+        gemm(A, B, a_kmaj=a_kmaj, b_kmaj=b_kmaj, out=acc, accumulate=True)
+        og = gemm(A, B, a_kmaj=a_kmaj, b_kmaj=b_kmaj, bias=r["bias"], act=2, aux_out=aux)
+        od = gemm(A, B, a_kmaj=a_kmaj, b_kmaj=b_kmaj, act_bwd=2, aux_in=r["z"], colsum=cs)
+    finally:
+        _lib.set_gemm_impl(-1)
+    assert len(explained) == 8
+    assert explained[0::2] == explained[1::2], explained
+    if K % 32 and (a_kmaj or b_kmaj):
+        assert explained == [0] * 8, explained  # no persistent kernel takes a k-major K % 32 != 0
+    assert rel_err(ob, r["plain"]) < 1e-2
+    assert rel_err(acc - acc0, r["plain"]) < 2e-3
+    assert rel_err(og, r["fwd"]) < 1e-2
+    assert rel_err(aux, r["fwd_aux"]) < 1e-2
+    assert rel_err(od, r["dgrad"]) < 1e-2
+    assert rel_err(cs, r["dgrad_cs"]) < 2e-3
 
 
 def test_gemm_identity_asymmetric():
