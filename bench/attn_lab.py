@@ -2,10 +2,15 @@
 
     python bench/attn_lab.py [--N 64 --S 1023 --H 12] [--rounds 5 --iters 10]
 
-Times the delta pre-pass, and the dK/dV and dQ kernels of the shipped hd-64 variant with the
-compile-time ablation bits of ``dpc_attn_bwd_lab`` (attention.hip): 1 = no tile loop, 2 = no
-per-row register loads, 4 = no epilogue stores, 8 = no ring prologue.  Variants interleave in
-rounds inside one process (median).  Ablated outputs are wrong by design.
+Times the shipped hd-64 dK/dV and dQ kernels (the dQ kernel with its fused delta pre-pass) with
+the compile-time ablation bits of ``dpc_attn_bwd_lab`` (attention.hip): 1 = no tile loop, 2 = no
+per-row register loads (in the dQ kernel that includes the O rows of the pre-pass), 4 = no
+epilogue stores, 8 = no ring prologue.  Variants interleave in rounds inside one process
+(median).  Ablated outputs are wrong by design; an ablated dQ kernel does not write delta / lse2,
+so one full dQ launch before the loop gives the dK/dV kernels valid rows to stream.
+
+The lab has not been timed in this form: the numbers on record (``profiles/r3_attn/``,
+``profiles/r4_attn/attn_lab.log``) come from the unfused dQ kernel and a separate pre-pass.
 """
 from __future__ import annotations
 
@@ -55,13 +60,13 @@ def run(which, abl):
         raise RuntimeError(f"dpc_attn_bwd_lab({which}, {abl}) -> {rc}")
 
 
-variants = [("pre", 0, 0)]
+variants = []
 names = {0: "full", 1: "no_loop", 2: "no_rowload", 4: "no_store", 6: "no_rowload_no_store",
          3: "no_loop_no_rowload", 5: "no_loop_no_store", 7: "prologue_only", 15: "empty"}
 for which, kname in ((1, "dkdv"), (2, "dq")):
     for abl in (0, 2, 4, 6, 1, 3, 5, 7, 15):
         variants.append((f"{kname}_{names[abl]}", which, abl))
-run(0, 0)
+run(2, 0)  # delta / lse2 for the dK/dV kernels
 for _, w, b in variants:
     run(w, b)
 torch.cuda.synchronize()

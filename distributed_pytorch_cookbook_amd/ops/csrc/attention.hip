@@ -21,11 +21,12 @@
 //
 // Pipeline (every kernel): the streamed 64-row tiles (K/V, or Q/dO + their per-row lse /
 // delta) arrive by LDS-DMA into a 4-slot ring, issued from inline asm two tiles ahead, so the
-// only wait is a counted vmcnt + barrier per tile at the top of the loop.  Inside a wave the
-// work of adjacent 32-row sub-blocks is software-pipelined: the score MFMAs of sub-block
-// j+1 sit in the same basic block as the softmax VALU of sub-block j (independent, so the
-// scheduler interleaves them), then the accumulate MFMAs of j -- a wave alternates MFMA and
-// VALU work on its own instead of relying on lock-stepped partner waves.
+// only wait is a counted vmcnt + barrier per tile at the top of the loop.  In the forward a
+// wave's work on adjacent tiles is software-pipelined: the score MFMAs of tile t+1 sit in the
+// same basic block as the softmax VALU of tile t (independent, so the scheduler interleaves
+// them), then the accumulate MFMAs of t -- a wave alternates MFMA and VALU work on its own
+// instead of relying on lock-stepped partner waves.  The backward kernels run each 32-row
+// sub-block in plain order (the pipelined form measured slower there).
 //
 // LDS image of a tile: the [64 rows][HD] bf16 tile is stored as 128-B physical rows (HD=64:
 // one row each; HD=32: two rows each) with the 16-B chunk swizzle
@@ -34,7 +35,6 @@
 // head sizes.
 #include "common.h"
 
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -340,12 +340,13 @@ __device__ __forceinline__ void xcd_work(int nblk, int& bh, int& i) {
 }
 
 // ------------------------------------------------------------------ forward
+// The head_dim 128 forward (the pair-stream kernels below run hd 32 / 64).
 // Workgroup = 128 queries (4 waves x 32, query on the lane), sweeping 64-key tiles.  Per tile
 // and wave: S^T of the NEXT tile (2 x NST MFMAs) overlaps this tile's softmax, then
-// O^T += V^T P^T (4 x NDT MFMAs).
-// PIPE: 0 = plain order, 1 = next tile's S^T beside this tile's softmax, 2 = 1 + the tile's
-// LDS fragments read up front and the MFMA / VALU interleave pinned (sched_group_barrier)
-template <int HD, int PIPE, int OCC>
+// O^T += V^T P^T (4 x NDT MFMAs).  (Round 2 also measured the plain order and a form with the
+// tile's LDS fragments read up front and the MFMA / VALU interleave pinned; at hd 64 neither beat
+// this one -- 297 and 265-277 against 260-266 us: profiles/r2_attn/variants.md.)
+template <int HD, int OCC>
 __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(AttnArgs p) {
   using A = AT<HD>;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NSLOT * 2 * A::TILE];  // [slot][K|V]
@@ -413,22 +414,6 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(AttnArgs p) {
     const bf16_t* lkn = smem + ((t + 1) % NSLOT) * 2 * A::TILE;
     const bf16_t* lv = smem + (t % NSLOT) * 2 * A::TILE + A::TILE;
     if (t > last_w) return;  // wave-uniform
-    if constexpr (PIPE == 0) qk(sc, lv - A::TILE);
-    // PIPE 2: the next tile's K row fragments and this tile's V^T fragments, read before the
-    // softmax so their LDS latency hides under it
-    bf16x8 kfr[2][A::NST], vfr[2][2][A::NDT];
-    if constexpr (PIPE == 2) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int st = 0; st < A::NST; ++st) kfr[kb][st] = row_frag<HD>(lkn, kb * 32, st, lane);
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int ss = 0; ss < 2; ++ss)
-#pragma unroll
-          for (int d = 0; d < A::NDT; ++d) vfr[kb][ss][d] = tr_frag<HD>(lv, kb * 32, ss, d * 32, lane);
-    }
     const int kt0 = t * KT;
     // Scores stay raw (unscaled) until the exponent: p = 2^(s*c - m) is one FMA + v_exp.
     const bool need_mask = (p.causal && kt0 + KT - 1 > q0) || (kt0 + KT > S) || pad;  // wave-uniform
@@ -470,48 +455,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(AttnArgs p) {
     }
     const float nmu = (m == -INFINITY) ? 0.f : -m;
     // ---- one basic block: next tile's S^T MFMAs || this tile's exponentials
-    if constexpr (PIPE == 2) {
-      float ls = 0.f;
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        zero16(sn[kb]);
-#pragma unroll
-        for (int st = 0; st < A::NST; ++st) sn[kb] = MFMA32(kfr[kb][st], qf[st], sn[kb]);
-      }
-      bf16x8 pb[2][2];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float e = fast_exp2(fmaf(sc[kb][r], c, nmu));
-          sc[kb][r] = e;
-          ls += e;
-        }
-        pb[kb][0] = acc_frag(sc[kb], 0);
-        pb[kb][1] = acc_frag(sc[kb], 1);
-#pragma unroll
-        for (int ss = 0; ss < 2; ++ss)
-#pragma unroll
-          for (int d = 0; d < A::NDT; ++d) o[d] = MFMA32(vfr[kb][ss][d], pb[kb][ss], o[d]);
-      }
-      l += ls;
-      // interleave: the 2 NST score MFMAs carry the first half's ~56 VALU, the first half's
-      // 2 NDT PV MFMAs the second half's, then the last PV MFMAs
-      constexpr int NQ = 2 * A::NST, NP = 2 * A::NDT;
-#pragma unroll
-      for (int i = 0; i < NQ; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 56 / NQ, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 56 / NP, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, NP, 0);
-      return;
-    }
-    if constexpr (PIPE == 1) qk(sn, lkn);
+    qk(sn, lkn);
     float ls = 0.f;
     bf16x8 pb[2][2];
 #pragma unroll
@@ -535,7 +479,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(AttnArgs p) {
           o[d] = MFMA32(tr_frag<HD>(lv, kb * 32, ss, d * 32, lane), pb[kb][ss], o[d]);
   };
   floatx16 s0[2], s1[2];
-  if constexpr (PIPE != 0) qk(s0, smem);
+  qk(s0, smem);
   for (int t = 0; t < ntiles; t += 2) {
     step(t, s0, s1);
     if (t + 1 < ntiles) step(t + 1, s1, s0);
@@ -576,21 +520,22 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(AttnArgs p) {
 // ring slot (a Q element is the block's 128 query rows as two 64-row images, read into
 // registers by the waves at the block start), so the ring never drains at the seam and no
 // global load sits in front of the first MFMA.
-// Softmax: the row sum comes from the PV MFMAs (a constant all-ones A operand: every row of
-// that accumulator is sum_k P -- 4 more MFMAs per tile instead of 32 v_add), the half-wave max
+// Softmax: the row sum is four independent v_add chains per lane (taking it from the PV MFMAs
+// through an all-ones A operand -- 4 more MFMAs per tile -- measured 231 against 218-227 us at
+// hd 64, and no better on a persistent grid: profiles/r5_attn/var_sweep_final.log), the half-wave max
 // combine is a v_permlane32_swap (no LDS round trip), masks are 32-bit compares of
 // compile-time key offsets.
-// Persistent form: a grid of at most two workgroups per CU walks the pair items (item i:
-// head bh = i / npr, pair pr = i % npr; workgroup b takes items local(b) + k * grid, where the
-// workgroups of one XCD hold a contiguous run of locals, so the items an XCD runs at once share
-// heads and K/V tiles in its L2) and the DMA stream runs on across items: the next item's Q
-// and first K/V tiles land while the current one finishes, and its O stores drain under the
-// next item's MFMAs.  (A grid of one workgroup per item is the non-persistent form.)
+// Items: item i is head bh = i / npr, pair pr = i % npr; workgroup b takes items
+// local(b) + k * grid, where the workgroups of one XCD hold a contiguous run of locals, so the
+// items an XCD runs at once share heads and K/V tiles in its L2.  The library launches one
+// workgroup per item; the kernel's item loop and cursors also carry the DMA stream across several
+// items per workgroup.
 struct PairItem {
   int bh, blk0, blk1, len0, len;
 };
 
-template <int HD, int OCC, bool LMFMA>
+// (the hd 32 forward below S = 512: the launchers' comment)
+template <int HD, int OCC>
 __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nitems) {
   using A = AT<HD>;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NSLOT * 2 * A::TILE];  // [slot][K|V] or [slot][Q lo|Q hi]
@@ -662,14 +607,17 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nit
   const float c = p.scale * LOG2E;
   bf16x8 qf[A::NST];
   float m = -INFINITY, l = 0.f;
-  constexpr int NO = A::NDT + (LMFMA ? 1 : 0);  // O^T blocks (+ the row-sum block)
-  floatx16 o[NO];
+  floatx16 o[A::NDT];
   int q0 = 0, q = 0, last_w = 0;
   // ---- consume cursor
   int c_k = 0, c_off = 0;
   PairItem c_it = is_it;
   int bh = c_it.bh, h = 0, n = 0;
   const unsigned char* pad = nullptr;
+
+  // (unused: the A operand of the removed MFMA row sum.  Without this dead local hipcc allocates
+  // this kernel's scalar registers differently and inverts one branch; it stays until a change
+  // that alters the kernel's code anyway, so that removing the variants changed no shipped code)
   bf16x8 ones;
 #pragma unroll
   for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
@@ -683,8 +631,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nit
     }
   };
   auto finish = [&]() {  // the block's O and lse
-    if constexpr (LMFMA) l = o[A::NDT][0];
-    else l += __shfl_xor(l, 32, 64);  // the two lane halves summed different key rows
+    l += __shfl_xor(l, 32, 64);  // the two lane halves summed different key rows
     if (q < S) {
       const float inv = l > 0.f ? __builtin_amdgcn_rcpf(l) : 0.f;
       // (the row offset is formed here, in 32 bits: a pointer held across the loop is
@@ -741,7 +688,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nit
       m = -INFINITY;
       l = 0.f;
 #pragma unroll
-      for (int d = 0; d < NO; ++d) zero16(o[d]);
+      for (int d = 0; d < A::NDT; ++d) zero16(o[d]);
       qk(sn, lsn);
       return;
     }
@@ -787,9 +734,9 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nit
       const float mn = fmaxf(m, mx);
       const float alpha = (m == -INFINITY) ? 1.f : fast_exp2(m - mn);
       m = mn;
-      if constexpr (!LMFMA) l *= alpha;
+      l *= alpha;
 #pragma unroll
-      for (int d = 0; d < NO; ++d) scale16(o[d], alpha);
+      for (int d = 0; d < A::NDT; ++d) scale16(o[d], alpha);
     }
     const float nmu = (m == -INFINITY) ? 0.f : -m;
     if (t + 1 <= last_w) qk(sn, lsn);  // next tile's scores beside this tile's exponentials
@@ -801,21 +748,19 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nit
       for (int r = 0; r < 16; ++r) {
         const float ex = fast_exp2(fmaf(sc[kb][r], c, nmu));
         sc[kb][r] = ex;
-        if constexpr (!LMFMA) lq[r & 3] += ex;
+        lq[r & 3] += ex;
       }
       pb[kb][0] = acc_frag(sc[kb], 0);
       pb[kb][1] = acc_frag(sc[kb], 1);
     }
-    if constexpr (!LMFMA) l += (lq[0] + lq[1]) + (lq[2] + lq[3]);
+    l += (lq[0] + lq[1]) + (lq[2] + lq[3]);
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
+      for (int ss = 0; ss < 2; ++ss)
 #pragma unroll
         for (int d = 0; d < A::NDT; ++d)
           o[d] = MFMA32(tr_frag<HD>(lv, kb * 32, ss, d * 32, lane), pb[kb][ss], o[d]);
-        if constexpr (LMFMA) o[A::NDT] = MFMA32(ones, pb[kb][ss], o[A::NDT]);
-      }
   };
   floatx16 s0[2], s1[2];
   for (int e = 0; e < total; e += 2) {
@@ -826,8 +771,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nit
   vm_wait<0>();  // the pieces issued past the end (empty descriptors) drained
 }
 
-// Forward, round 6 (DPC_ATTN_VAR 9 / 10): attn_fwd2_kernel's pair stream, DMA ring and math with
-// the consume side split by tile kind.  fwd2 ran ONE step body for every element (block start,
+// Forward, round 6 (hd 64, and hd 32 from S = 512): attn_fwd2_kernel's pair stream, DMA ring and
+// math with the consume side split by tile kind.  fwd2 ran ONE step body for every element (block start,
 // masked tile, skipped tile, plain tile), and at its joins the compiler copied the score and O
 // accumulators: 48 v_mov_b64 per plain tile in its gfx950 listing, ~1/4 of the tile's VALU.  Here,
 // per block and wave, the leading tiles that need no mask and have a successor tile run in a
@@ -835,7 +780,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd2_kernel(AttnArgs p, int nit
 // formed, the lazy rescale's branch inside asm: scale16_if); the block's other tiles -- the
 // causal diagonal, past the end, padded, or skipped by this wave -- take the general body one
 // at a time, with one explicit copy of the next scores each.
-template <int HD, int OCC, bool LMFMA>
+template <int HD, int OCC>
 __global__ __launch_bounds__(256, OCC) void attn_fwd3_kernel(AttnArgs p, int nitems) {
   using A = AT<HD>;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NSLOT * 2 * A::TILE];  // [slot][K|V] or [slot][Q lo|Q hi]
@@ -909,14 +854,10 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd3_kernel(AttnArgs p, int nit
   const float c = p.scale * LOG2E;
   bf16x8 qf[A::NST];
   float m = -INFINITY, l = 0.f;
-  constexpr int NO = A::NDT + (LMFMA ? 1 : 0);  // O^T blocks (+ the row-sum block)
-  floatx16 o[NO];
+  floatx16 o[A::NDT];
   int q0 = 0, q = 0, last_w = 0;
   int bh = 0, h = 0, n = 0;
   const unsigned char* pad = nullptr;
-  bf16x8 ones;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ones[i] = (__bf16)1.0f;
 
   auto qk = [&](floatx16 (&s)[2], const bf16_t* lk) {
 #pragma unroll
@@ -927,8 +868,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd3_kernel(AttnArgs p, int nit
     }
   };
   auto finish = [&]() {  // the block's O and lse
-    if constexpr (LMFMA) l = o[A::NDT][0];
-    else l += __shfl_xor(l, 32, 64);
+    l += __shfl_xor(l, 32, 64);
     if (q < S) {
       const float inv = l > 0.f ? __builtin_amdgcn_rcpf(l) : 0.f;
       bf16_t* O = static_cast<bf16_t*>(p.o) + (long long)n * S * p.ld_o + h * HD + q * (int)p.ld_o;
@@ -992,16 +932,15 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd3_kernel(AttnArgs p, int nit
         const float mn = fmaxf(m, mx);
         const float alpha = (m == -INFINITY) ? 1.f : fast_exp2(m - mn);
         m = mn;
-        if constexpr (!LMFMA) l *= alpha;
+        l *= alpha;
 #pragma unroll
-        for (int d = 0; d < NO; ++d) scale16(o[d], alpha);
+        for (int d = 0; d < A::NDT; ++d) scale16(o[d], alpha);
       }
     } else {
-      static_assert(!LMFMA, "plain tiles: the row sum in l");
       const unsigned long long up = __ballot(mx > m + 8.f);
       const float alpha = rescale16_if(o[0], m, l, mx, up);
 #pragma unroll
-      for (int d = 1; d < NO; ++d) scale16_if(o[d], alpha, up);
+      for (int d = 1; d < A::NDT; ++d) scale16_if(o[d], alpha, up);
     }
     // (a plain tile has no masked score, so m is finite after its update)
     const float nmu = (!GEN || m != -INFINITY) ? -m : 0.f;
@@ -1018,21 +957,19 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd3_kernel(AttnArgs p, int nit
       for (int r = 0; r < 16; ++r) {
         const float ex = fast_exp2(fmaf(sc[kb][r], c, nmu));
         sc[kb][r] = ex;
-        if constexpr (!LMFMA) lq[r & 3] += ex;
+        lq[r & 3] += ex;
       }
       pb[kb][0] = acc_frag(sc[kb], 0);
       pb[kb][1] = acc_frag(sc[kb], 1);
     }
-    if constexpr (!LMFMA) l += (lq[0] + lq[1]) + (lq[2] + lq[3]);
+    l += (lq[0] + lq[1]) + (lq[2] + lq[3]);
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int ss = 0; ss < 2; ++ss) {
+      for (int ss = 0; ss < 2; ++ss)
 #pragma unroll
         for (int d = 0; d < A::NDT; ++d)
           o[d] = MFMA32(tr_frag<HD>(lv, kb * 32, ss, d * 32, lane), pb[kb][ss], o[d]);
-        if constexpr (LMFMA) o[A::NDT] = MFMA32(ones, pb[kb][ss], o[A::NDT]);
-      }
   };
   using Plain = std::integral_constant<bool, false>;
   using General = std::integral_constant<bool, true>;
@@ -1066,7 +1003,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd3_kernel(AttnArgs p, int nit
       m = -INFINITY;
       l = 0.f;
 #pragma unroll
-      for (int d = 0; d < NO; ++d) zero16(o[d]);
+      for (int d = 0; d < A::NDT; ++d) zero16(o[d]);
       qk(sA, slot(e + 1));
       ++e;
       // ---- plain tiles: no mask (inside S, no padding, wholly at or below the wave's first
@@ -1104,47 +1041,15 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd3_kernel(AttnArgs p, int nit
 }
 
 // ------------------------------------------------------------------ backward
-// delta[n,h,s] = sum_d dO * O   (one HD/8-lane group per (token, head)), stored NEGATED (the
-// dK / dV kernel's dP accumulator starts at -delta: an LDS read straight into it, no per-element
-// sign flip), and the second half of the buffer the row's lse in log2 units (lse * log2 e) --
-// the kernels then form p = 2^(s c - lse2) with one FMA and no per-element multiply
-template <int HD>
-__global__ __launch_bounds__(256) void attn_bwd_pre_kernel(AttnArgs p) {
-  constexpr int G = HD / 8;
-  const long long T = (long long)p.N * p.S;
-  const long long row = ((long long)blockIdx.x * 256 + threadIdx.x) / G;  // (token, head)
-  const int sub = threadIdx.x % G;
-  float acc = 0.f;
-  long long t = 0;
-  int h = 0;
-  if (row < T * p.H) {
-    t = row / p.H;
-    h = (int)(row % p.H);
-    const bf16_t* o = static_cast<const bf16_t*>(p.o) + t * p.ld_o + h * HD + sub * 8;
-    const bf16_t* d = static_cast<const bf16_t*>(p.dout) + t * p.ld_o + h * HD + sub * 8;
-    float fo[8], fd[8];
-    unpack8(*reinterpret_cast<const uint4*>(o), fo);
-    unpack8(*reinterpret_cast<const uint4*>(d), fd);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc += fo[i] * fd[i];
-  }
-#pragma unroll
-  for (int o = 1; o < G; o <<= 1) acc += __shfl_xor(acc, o, 64);
-  if (row < T * p.H && sub == 0) {
-    const long long n = t / p.S, s = t % p.S;
-    const long long i = (n * p.H + h) * p.S + s;
-    p.delta[i] = -acc;
-    p.delta[T * p.H + i] = p.lse[i] * LOG2E;  // (+inf stays +inf: a fully masked row)
-  }
-}
-
-// dK, dV: workgroup = 128 keys (4 waves x 32, key on the lane), sweeping the 64-query tiles
-// at or after the first key.  Per 32-query sub-block j: S, dP of sub-block j+1 (2 x NST
-// MFMAs) overlap the P / dS arithmetic of j, then dV^T, dK^T += ... (4 x NDT MFMAs).
+// dK, dV (launched after the dQ kernel, which writes the delta / lse2 rows streamed here):
+// workgroup = 128 keys (4 waves x 32, key on the lane), sweeping the 64-query tiles at or after
+// the first key.  Per 32-query sub-block: S, dP (2 x NST MFMAs), the P / dS arithmetic, then
+// dV^T, dK^T += ... (4 x NDT MFMAs), in plain order (forming the next sub-block's S, dP beside
+// this one's arithmetic measured slower: 882 against 847 us at hd 64, profiles/r2_attn/variants.md).
 // ABL (dpc_attn_bwd_lab only; the library launches ABL = 0): per-workgroup cost ablations --
 // 1 = no tile loop (the ring prologue stays), 2 = no per-row register loads, 4 = no epilogue
 // stores, 8 = no ring prologue.  Outputs are wrong by design.
-template <int HD, bool PIPE, int OCC, int ABL = 0>
+template <int HD, int OCC, int ABL = 0>
 __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(AttnArgs p) {
   using A = AT<HD>;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NSLOT * 2 * A::TILE];  // [slot][Q|dO]
@@ -1258,25 +1163,17 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(AttnArgs p) {
     else vm_wait<4 * A::NPW>();
     ring_barrier();
   }
-  // sub-block (tile i, half hf): its S / dP in (sa, dp); the next sub-block's land in (san, dpn)
-  auto half = [&](int i, int hf, floatx16& sa, floatx16& dp, floatx16& san, floatx16& dpn) {
+  // sub-block (tile i, half hf); (sa, dp): its S / dP registers, a pair of its own for each half
+  auto half = [&](int i, int hf, floatx16& sa, floatx16& dp) {
     const int slot = i % NSLOT;
     const bf16_t* lq = smem + slot * 2 * A::TILE;
     const bf16_t* ldo = lq + A::TILE;
-    // the next sub-block: second half of this tile, or first half of the next tile
-    const bf16_t* nq = hf == 0 ? lq : smem + ((i + 1) % NSLOT) * 2 * A::TILE;
-    const int nr0 = hf == 0 ? 32 : 0;
     const int qt0 = (qt_begin + i) * KT;
     const int qs0 = qt0 + 32 * hf;
     const bool active = !(p.causal && qs0 + 31 < k0);  // wave-uniform: some query >= some key
-    if (!active) {
-      if constexpr (PIPE) sdp(san, dpn, nq, nr0);
-      return;
-    }
+    if (!active) return;
     const bool diag = p.causal && qs0 < k0 + 31;  // wave-uniform: some key > some query
-    // ---- one basic block: next S, dP MFMAs || this sub-block's P, dS
-    if constexpr (PIPE) sdp(san, dpn, nq, nr0);
-    else sdp(sa, dp, lq, 32 * hf);
+    sdp(sa, dp, lq, 32 * hf);
     // P, dS.  The causal zeroing runs only on the sub-blocks that cross the diagonal, in place,
     // between the exponentials and the dS products: written as a select inside the element loop,
     // hipcc if-converted it into an add, a compare, an exec-mask AND and a select on EVERY element
@@ -1311,14 +1208,13 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(AttnArgs p) {
     }
   };
   floatx16 sa0, dp0, sa1, dp1;
-  if constexpr (PIPE) sdp(sa0, dp0, smem, 0);
   for (int i = 0; i < ((ABL & 1) ? 0 : count); ++i) {
     if (wid == 0) vm_wait<2 * A::NPW + 2>();  // tile i+1 landed (i+2 may fly)
     else vm_wait<2 * A::NPW>();
     ring_barrier();
     issue(i + 3);
-    half(i, 0, sa0, dp0, sa1, dp1);
-    half(i, 1, sa1, dp1, sa0, dp0);
+    half(i, 0, sa0, dp0);
+    half(i, 1, sa1, dp1);
   }
   vm_wait<0>();
 
@@ -1352,13 +1248,16 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dkdv_kernel(AttnArgs p) {
 }
 
 // dQ: workgroup = 128 queries (4 waves x 32, query on the lane), sweeping the key tiles up to
-// the last query.  Per 32-key sub-block j: S^T, dP^T of j+1 overlap dS^T of j, then
-// dQ^T += K^T dS^T (2 x NDT MFMAs).
-// PRE: the delta pre-pass fused in (the default): the kernel also loads its query rows of O,
-// forms delta = rowsum(dO * O) itself (each lane holds half of a row, the other half on lane
-// ^ 32) and writes delta and the log2-unit lse rows that the dK / dV kernel -- launched after
-// it -- streams.  Saves attn_bwd_pre_kernel's pass over O and dO (the dQ kernel holds dO anyway).
-template <int HD, bool PIPE, int OCC, int ABL = 0, bool PRE = false>  // (ABL: as attn_bwd_dkdv_kernel)
+// the last query.  Per 32-key sub-block: S^T, dP^T, then dS^T, then dQ^T += K^T dS^T
+// (2 x NDT MFMAs), in plain order as the dK / dV kernel.
+// The delta pre-pass is fused in: the kernel also loads its query rows of O, forms
+// delta = rowsum(dO * O) itself (each lane holds half of a row, the other half on lane ^ 32) and
+// writes delta and the log2-unit lse rows that the dK / dV kernel -- launched after it --
+// streams.  Saves a separate kernel's pass over O and dO (the dQ kernel holds dO anyway).
+// ABL: as attn_bwd_dkdv_kernel; the O rows count as per-row register loads (bit 2), and an
+// ablated kernel does not write delta / lse2, so that the buffer stays valid for the dK / dV
+// kernel whatever ran before it.
+template <int HD, int OCC, int ABL = 0>
 __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnArgs p) {
   using A = AT<HD>;
   __shared__ __attribute__((aligned(16))) bf16_t smem[NSLOT * 2 * A::TILE];  // [slot][K|V]
@@ -1387,31 +1286,29 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnArgs p) {
     df[st] = (q < S && !(ABL & 2)) ? load_row8(dO + (tok0 + q) * p.ld_o + 16 * st + 8 * hh) : bf16x8{};
   }
   const float c = p.scale * LOG2E;
-  float lse2, dl;
-  if constexpr (PRE) {
-    const bf16_t* Op = static_cast<const bf16_t*>(p.o) + h * HD;
-    float acc = 0.f;
-    if (q < S) {
+  const bf16_t* Op = static_cast<const bf16_t*>(p.o) + h * HD;
+  float acc = 0.f;
+  if (q < S && !(ABL & 2)) {
 #pragma unroll
-      for (int st = 0; st < A::NST; ++st) {
-        const bf16x8 of = load_row8(Op + (tok0 + q) * p.ld_o + 16 * st + 8 * hh);
-        float fo[8], fd[8];
-        unpack8(__builtin_bit_cast(uint4, of), fo);
-        unpack8(__builtin_bit_cast(uint4, df[st]), fd);
+    for (int st = 0; st < A::NST; ++st) {
+      const bf16x8 of = load_row8(Op + (tok0 + q) * p.ld_o + 16 * st + 8 * hh);
+      float fo[8], fd[8];
+      unpack8(__builtin_bit_cast(uint4, of), fo);
+      unpack8(__builtin_bit_cast(uint4, df[st]), fd);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc = fmaf(fo[i], fd[i], acc);
-      }
+      for (int i = 0; i < 8; ++i) acc = fmaf(fo[i], fd[i], acc);
     }
-    dl = acc + __shfl_xor(acc, 32, 64);  // (the row's other half on lane ^ 32)
-    // (+inf stays +inf: a fully masked row)
-    lse2 = q < S ? p.lse[(long long)bh * S + q] * LOG2E : INFINITY;
-    if (q < S && hh == 0) {
-      p.delta[(long long)bh * S + q] = -dl;  // (negated: attn_bwd_pre_kernel)
-      p.delta[(long long)p.N * H * S + (long long)bh * S + q] = lse2;
-    }
-  } else {
-    lse2 = q < S ? p.delta[(long long)p.N * H * S + (long long)bh * S + q] : INFINITY;
-    dl = q < S ? -p.delta[(long long)bh * S + q] : 0.f;
+  }
+  const float dl = acc + __shfl_xor(acc, 32, 64);  // (the row's other half on lane ^ 32)
+  // (+inf stays +inf: a fully masked row)
+  const float lse2 = q < S ? p.lse[(long long)bh * S + q] * LOG2E : INFINITY;
+  // delta[n,h,s] = sum_d dO * O is stored NEGATED (the dK / dV kernel's dP accumulator starts at
+  // -delta: an LDS read straight into it, no per-element sign flip), and the second half of the
+  // buffer holds the row's lse in log2 units (lse * log2 e) -- the kernels then form
+  // p = 2^(s c - lse2) with one FMA and no per-element multiply
+  if (q < S && hh == 0 && ABL == 0) {
+    p.delta[(long long)bh * S + q] = -dl;
+    p.delta[(long long)p.N * H * S + (long long)bh * S + q] = lse2;
   }
   pin_loaded(qf);
   pin_loaded(df);
@@ -1452,21 +1349,15 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnArgs p) {
     vm_wait<4 * A::NPW>();  // tile 0 landed (tiles 1, 2 may fly)
     ring_barrier();
   }
-  auto half = [&](int t, int hf, floatx16& sa, floatx16& dp, floatx16& san, floatx16& dpn) {
+  // sub-block (tile t, half hf); (sa, dp): its S^T / dP^T registers, a pair of its own for each half
+  auto half = [&](int t, int hf, floatx16& sa, floatx16& dp) {
     const bf16_t* lk = smem + (t % NSLOT) * 2 * A::TILE;
-    const bf16_t* nk = hf == 0 ? lk : smem + ((t + 1) % NSLOT) * 2 * A::TILE;
-    const int nr0 = hf == 0 ? 32 : 0;
     const int kt0 = t * KT;
     const int ks0 = kt0 + 32 * hf;
     const bool active = !(p.causal && ks0 > q0 + 31);  // wave-uniform: some key <= some query
-    if (!active) {
-      if constexpr (PIPE) sdp(san, dpn, nk, nr0);
-      return;
-    }
+    if (!active) return;
     const bool need_mask = (p.causal && ks0 + 31 > q0) || (ks0 + 32 > S) || pad;  // wave-uniform
-    // ---- one basic block: next S^T, dP^T MFMAs || this sub-block's dS^T
-    if constexpr (PIPE) sdp(san, dpn, nk, nr0);
-    else sdp(sa, dp, lk, 32 * hf);
+    sdp(sa, dp, lk, 32 * hf);
     if (need_mask) {
       const unsigned long long pm = pad_bits(pad, kt0, S, lane);
       const int lim = (p.causal ? min(q, S - 1) : S - 1) - kt0;
@@ -1490,13 +1381,12 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnArgs p) {
     }
   };
   floatx16 sa0, dp0, sa1, dp1;
-  if constexpr (PIPE) sdp(sa0, dp0, smem, 0);
   for (int t = 0; t < ((ABL & 1) ? 0 : ntiles); ++t) {
     vm_wait<2 * A::NPW>();  // this wave's pieces of tile t+1 landed (t+2 may fly)
     ring_barrier();         // ... every wave's; and every wave is done with tile t-1's slot
     issue(t + 3);
-    half(t, 0, sa0, dp0, sa1, dp1);
-    half(t, 1, sa1, dp1, sa0, dp0);
+    half(t, 0, sa0, dp0);
+    half(t, 1, sa1, dp1);
   }
   vm_wait<0>();
 
@@ -1516,93 +1406,47 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnArgs p) {
   }
 }
 
-// kernel variant (env DPC_ATTN_VAR="<fwd>,<bwd>", measured on MI355X: bench/attn_one.py):
-// 0 = software-pipelined, 2 workgroups / CU; 1 = plain order, 2 / CU; 2 = plain, 3 / CU;
-// 3 = pipelined, 3 / CU; 4 (forward only) = pipelined + fragments up front + pinned interleave;
-// forward only: 5 / 6 = pair stream (attn_fwd2_kernel) with / without the MFMA row sum,
-// 7 / 8 = the same on a persistent grid, 9 = 6 with the tile loop split by kind (attn_fwd3_kernel;
-// its MFMA-row-sum form spilled 80 registers and ran 272 us, so it is not built).
-// Defaults per head size (GPT-2 small shape, B=64 S=1023 H=12, profiles/r2_attn/, round 6:
-// profiles/r6_attn/):  hd 64: forward 9, backward 1;  hd 32: forward 6 (S < 512) / 9, backward 2.
-static int g_attn_env[2] = {-2, -2};
-static int attn_var(int hd, int bwd, int S = 0) {
-  if (g_attn_env[0] == -2) {
-    g_attn_env[0] = g_attn_env[1] = -1;
-    if (const char* e = getenv("DPC_ATTN_VAR")) sscanf(e, "%d,%d", &g_attn_env[0], &g_attn_env[1]);
-  }
-  if (g_attn_env[bwd] >= 0) return g_attn_env[bwd];
-  // hd 32 forward (round 6, profiles/r6_attn/hd32_fwd_variants.log): the pair streams beat the
-  // per-block kernel (2) -- fwd2 (6) at the reference CLI default S = 255 (16.9 vs 18.2 us),
-  // fwd3 (9) at S = 1023 (111.3 vs 120.5 us)
-  if (hd == 32) return bwd ? 2 : (S < 512 ? 6 : 9);
-  return bwd ? 1 : 9;
-}
-
-#define DPC_ATTN_SWITCH(var, KERNEL, ...)                                                   \
-  switch (var) {                                                                           \
-    case 0: hipLaunchKernelGGL((KERNEL<HD, true, 2>), __VA_ARGS__); break;                  \
-    case 1: hipLaunchKernelGGL((KERNEL<HD, false, 2>), __VA_ARGS__); break;                 \
-    case 3: hipLaunchKernelGGL((KERNEL<HD, true, 3>), __VA_ARGS__); break;                  \
-    default: hipLaunchKernelGGL((KERNEL<HD, false, 3>), __VA_ARGS__); break;                \
-  }
-
-// head_dim 128 (e.g. main-single.py --head_dim 128; 96 and other sizes over 64 are padded up to
-// it): the same kernels at one workgroup per CU -- the 4-slot ring of K|V (or Q|dO) tiles is
-// 4 x 2 x 16 KiB = 128 KiB of LDS, and the doubled Q / O (K, V, dK, dV) register rows need the
-// 512-register budget.  (Correctness path; the GPT-2 presets run hd 64.)
-static int launch_fwd128(const AttnArgs* a, hipStream_t stream) {
-  dim3 grid((unsigned)(((a->S + QB - 1) / QB) * a->N * a->H));
-  hipLaunchKernelGGL((attn_fwd_kernel<128, 1, 1>), grid, dim3(256), 0, stream, *a);
-  return (int)hipGetLastError();
-}
-static int launch_bwd128(const AttnArgs* a, hipStream_t stream) {
-  dim3 grid((unsigned)(((a->S + QB - 1) / QB) * a->N * a->H));
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<128, false, 1, 0, true>), grid, dim3(256), 0, stream, *a);
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<128, false, 1>), grid, dim3(256), 0, stream, *a);
-  return (int)hipGetLastError();
-}
-
-template <int HD>
+// ------------------------------------------------------------------ launchers
+// Which kernel runs, and at how many workgroups per CU (all measured on MI355X, GPT-2 small shape
+// N = 64, H = 12 unless noted; bench/attn_time.py, bench/attn_one.py):
+//   forward   hd 64 and hd 32 run the pair stream: with its tile loop removed, the per-block
+//             kernel (attn_fwd_kernel) still took 76 of its 267 us at S = 1023 (attn_fwd2_kernel's
+//             header).  hd 64: attn_fwd3_kernel.  hd 32, round 6
+//             (profiles/r6_attn/hd32_fwd_variants.log): against the per-block kernel at three
+//             workgroups per CU, attn_fwd2_kernel won at S = 255 (16.9 against 18.2 us) and
+//             attn_fwd3_kernel at S = 1023 (111.3 against 120.5 us); hence the switch at S = 512.
+//   backward  the dQ kernel first (it writes delta / lse2), then dK / dV, both in plain order at
+//             two workgroups per CU for hd 64 and three for hd 32 (profiles/r2_attn/variants.md).
+//             Round 4 measured persistent pair-stream forms of both kernels -- one LDS-DMA stream
+//             of (heaviest, lightest) block pairs per workgroup -- bitwise equal but slower: bwd
+//             754 -> 798 us with the dK / dV stream, 770 -> 954 us with the dQ stream, DDP step
+//             -0.8 % / -4 % (profiles/r4_attn/).
+//   hd 128    (e.g. main-single.py --head_dim 128; 96 and other sizes over 64 are padded up to
+//             it) one workgroup per CU: the 4-slot ring of K|V (or Q|dO) tiles is 4 x 2 x 16 KiB
+//             = 128 KiB of LDS, and the doubled Q / O (K, V, dK, dV) register rows need the
+//             512-register budget.  (Correctness path; the GPT-2 presets run hd 64.)
 static int launch_fwd(const AttnArgs* a, hipStream_t stream) {
-  const int var = attn_var(HD, 0, a->S);
-  dim3 grid((unsigned)(((a->S + QB - 1) / QB) * a->N * a->H));  // 1-D: xcd_work() maps it
-  if (var >= 5 && var <= 9) {  // pair stream (attn_fwd2_kernel); 7, 8: persistent grid; 9: = 6 with
-    // the tile loop split by kind (attn_fwd3_kernel)
-    const int nqb = (a->S + QB - 1) / QB;
-    const int nitems = ((nqb + 1) / 2) * a->N * a->H;
-    dim3 g2((unsigned)((var == 7 || var == 8) && nitems > 512 ? 512 : nitems));
-    if (var == 9) hipLaunchKernelGGL((attn_fwd3_kernel<HD, 2, false>), g2, dim3(256), 0, stream, *a, nitems);
-    else if (var == 5 || var == 8) hipLaunchKernelGGL((attn_fwd2_kernel<HD, 2, true>), g2, dim3(256), 0, stream, *a, nitems);
-    else hipLaunchKernelGGL((attn_fwd2_kernel<HD, 2, false>), g2, dim3(256), 0, stream, *a, nitems);
-  } else if (var == 4) hipLaunchKernelGGL((attn_fwd_kernel<HD, 2, 2>), grid, dim3(256), 0, stream, *a);
-  else DPC_ATTN_SWITCH(var, attn_fwd_kernel, grid, dim3(256), 0, stream, *a);
+  const int nqb = (a->S + QB - 1) / QB;
+  const dim3 blocks((unsigned)(nqb * a->N * a->H));  // one workgroup per 128-query block (xcd_work() maps it)
+  const int nitems = ((nqb + 1) / 2) * a->N * a->H;  // pair stream: one workgroup per pair of blocks
+  const dim3 pairs((unsigned)nitems);
+  if (a->hd == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, 1>), blocks, dim3(256), 0, stream, *a);
+  else if (a->hd == 64) hipLaunchKernelGGL((attn_fwd3_kernel<64, 2>), pairs, dim3(256), 0, stream, *a, nitems);
+  else if (a->S < 512) hipLaunchKernelGGL((attn_fwd2_kernel<32, 2>), pairs, dim3(256), 0, stream, *a, nitems);
+  else hipLaunchKernelGGL((attn_fwd3_kernel<32, 2>), pairs, dim3(256), 0, stream, *a, nitems);
   return (int)hipGetLastError();
 }
 
-// The shipped backward (variant 1 at hd 64, 2 at hd 32): the dQ kernel first, with the delta
-// pre-pass fused in (it writes delta / lse2 for the dK / dV kernel); DPC_ATTN_PRE=1 (or a forced
-// variant) keeps the separate pre-pass kernel and the dK / dV -> dQ order.
-template <int HD>
+template <int HD, int OCC>
+static void launch_bwd_at(const AttnArgs* a, dim3 blocks, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, OCC>), blocks, dim3(256), 0, stream, *a);
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<HD, OCC>), blocks, dim3(256), 0, stream, *a);
+}
 static int launch_bwd(const AttnArgs* a, hipStream_t stream) {
-  const int var = attn_var(HD, 1);
-  static int pre_env = -1;
-  if (pre_env < 0) pre_env = getenv("DPC_ATTN_PRE") ? atoi(getenv("DPC_ATTN_PRE")) : 0;
-  dim3 grid((unsigned)(((a->S + QB - 1) / QB) * a->N * a->H));
-  // (round 4 measured persistent pair-stream forms of both kernels -- one LDS-DMA stream of
-  // (heaviest, lightest) block pairs per workgroup -- bitwise equal but slower: bwd 754 -> 798 us
-  // with the dK / dV stream, 770 -> 954 us with the dQ stream, DDP step -0.8 % / -4 %
-  // (profiles/r4_attn/); removed)
-  if (!pre_env && var == (HD == 32 ? 2 : 1)) {
-    if (HD == 32) hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, false, 3, 0, true>), grid, dim3(256), 0, stream, *a);
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<HD, false, 2, 0, true>), grid, dim3(256), 0, stream, *a);
-    DPC_ATTN_SWITCH(var, attn_bwd_dkdv_kernel, grid, dim3(256), 0, stream, *a);
-    return (int)hipGetLastError();
-  }
-  const long long rows = (long long)a->N * a->S * a->H;
-  dim3 gpre((unsigned)((rows * (HD / 8) + 255) / 256));
-  hipLaunchKernelGGL(attn_bwd_pre_kernel<HD>, gpre, dim3(256), 0, stream, *a);
-  DPC_ATTN_SWITCH(var, attn_bwd_dkdv_kernel, grid, dim3(256), 0, stream, *a);
-  DPC_ATTN_SWITCH(var, attn_bwd_dq_kernel, grid, dim3(256), 0, stream, *a);
+  const dim3 blocks((unsigned)(((a->S + QB - 1) / QB) * a->N * a->H));  // one workgroup per 128 rows
+  if (a->hd == 128) launch_bwd_at<128, 1>(a, blocks, stream);
+  else if (a->hd == 64) launch_bwd_at<64, 2>(a, blocks, stream);
+  else launch_bwd_at<32, 3>(a, blocks, stream);
   return (int)hipGetLastError();
 }
 
@@ -1623,26 +1467,21 @@ static bool attn_args_ok(const AttnArgs* a, bool bwd) {
 
 DPC_API int dpc_attn_fwd(const AttnArgs* a, hipStream_t stream) {
   if (!attn_args_ok(a, false)) return (int)hipErrorInvalidValue;
-  if (a->hd == 128) return launch_fwd128(a, stream);
-  return a->hd == 32 ? launch_fwd<32>(a, stream) : launch_fwd<64>(a, stream);
+  return launch_fwd(a, stream);
 }
 
-// Lab entry (bench/attn_lab.py): one backward kernel (which: 0 = delta / lse pre-pass, 1 = dK / dV,
-// 2 = dQ) of the hd-64 shipped variant (plain order, 2 workgroups per CU) with the
-// per-workgroup cost ablation bits ABL (attn_bwd_dkdv_kernel).
+// Lab entry (bench/attn_lab.py): one backward kernel (which: 1 = dK / dV, 2 = dQ with its fused
+// delta pre-pass) of the shipped hd-64 form (2 workgroups per CU) with the per-workgroup cost
+// ablation bits ABL (attn_bwd_dkdv_kernel).  ABL = 0 is the shipped kernel itself.
 template <int ABL>
 static void attn_lab_launch(const AttnArgs* a, int which, hipStream_t stream) {
   dim3 grid((unsigned)(((a->S + QB - 1) / QB) * a->N * a->H));
-  if (which == 1) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<64, false, 2, ABL>), grid, dim3(256), 0, stream, *a);
-  else hipLaunchKernelGGL((attn_bwd_dq_kernel<64, false, 2, ABL>), grid, dim3(256), 0, stream, *a);
+  if (which == 1) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<64, 2, ABL>), grid, dim3(256), 0, stream, *a);
+  else hipLaunchKernelGGL((attn_bwd_dq_kernel<64, 2, ABL>), grid, dim3(256), 0, stream, *a);
 }
 DPC_API int dpc_attn_bwd_lab(const AttnArgs* a, int which, int abl, hipStream_t stream) {
   if (!attn_args_ok(a, true) || a->hd != 64) return (int)hipErrorInvalidValue;
-  if (which == 0) {
-    const long long rows = (long long)a->N * a->S * a->H;
-    hipLaunchKernelGGL(attn_bwd_pre_kernel<64>, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, stream, *a);
-    return (int)hipGetLastError();
-  }
+  if (which != 1 && which != 2) return (int)hipErrorInvalidValue;  // (0 was the separate pre-pass kernel)
   switch (abl) {
     case 0: attn_lab_launch<0>(a, which, stream); break;
     case 1: attn_lab_launch<1>(a, which, stream); break;
@@ -1677,6 +1516,5 @@ DPC_API int dpc_attn_bwd(const AttnArgs* a_in, hipStream_t stream) {
   b.order = attn_order();
   const AttnArgs* a = &b;
   if (!attn_args_ok(a, true)) return (int)hipErrorInvalidValue;
-  if (a->hd == 128) return launch_bwd128(a, stream);
-  return a->hd == 32 ? launch_bwd<32>(a, stream) : launch_bwd<64>(a, stream);
+  return launch_bwd(a, stream);
 }

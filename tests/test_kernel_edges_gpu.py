@@ -203,7 +203,10 @@ def _pad_mask(N, S):
 
 
 ATTN_CASES = ([(hd, S, True, wp) for hd in (32, 64, 128, 96) for S in (1, 63, 65, 129, 200) for wp in (False, True)]
-              + [(hd, 129, False, False) for hd in (32, 64, 128, 96)])
+              + [(hd, 129, False, False) for hd in (32, 64, 128, 96)]
+              # the hd 32 forward changes kernel at S = 512; 513 is 5 query blocks, so the middle
+              # block pairs with itself
+              + [(32, S, True, wp) for S in (511, 513) for wp in (False, True)])
 
 
 @pytest.mark.parametrize("hd,S,causal,with_pad", ATTN_CASES)
