@@ -44,6 +44,12 @@ def build_parser(recipe: str = "single") -> argparse.ArgumentParser:
     p.add_argument("--grad_scaler", action="store_true",
                    help="dynamic loss scaling as the reference's GradScaler (fused non-finite check, "
                         "skip + back-off on device); unnecessary for bf16, off by default")
+    p.add_argument("--max_grad_norm", type=float, default=0.0,
+                   help="clip the global gradient norm to this value (torch's clip_grad_norm_ semantics, on "
+                        "the device, inside the captured step; 0 = off).  The norm must be known before any "
+                        "parameter moves, so the optimizer runs after every gradient collective has finished: "
+                        "the bucket-by-bucket (DDP, PP x DP) and unit-by-unit (FSDP) AdamW overlap is not "
+                        "available with clipping")
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--recompute", action="store_true",
                    help="activation recompute: keep only each layer's input, re-run its forward in backward")

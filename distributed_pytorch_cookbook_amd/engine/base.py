@@ -21,6 +21,20 @@ class Engine:
     is_logger = True          # this rank prints / saves
     scaler = None             # ops.amp.GradScaler when --grad_scaler (reference GradScaler)
 
+    clipper = None            # ops.clip.GradClipper when --max_grad_norm > 0
+
+    def _make_clipper(self, max_grad_norm: float) -> None:
+        if max_grad_norm and max_grad_norm > 0.0:
+            from ..ops.clip import GradClipper
+
+            self.clipper = GradClipper(max_grad_norm, self.device)
+
+    @property
+    def grad_norm(self):
+        """Global gradient norm of the last step before clipping (a 0-dim device tensor; the same
+        on every rank), or None without --max_grad_norm."""
+        return None if self.clipper is None else self.clipper.norm_t
+
     def _scaled(self, loss):
         return self.scaler.scale(loss) if self.scaler is not None else loss
 

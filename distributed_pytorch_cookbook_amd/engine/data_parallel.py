@@ -28,7 +28,7 @@ class DataParallelEngine(Engine):
     def __init__(self, model, device, lr: float, group=None, bucket_mb: float = 128.0,
                  reduce_dtype=torch.float32, overlap: bool = True, compute_dtype=None,
                  graph: bool = False, comm_kind: str | None = None, grad_scaler: bool = False,
-                 force_ddp_store: bool = False):
+                 force_ddp_store: bool = False, max_grad_norm: float = 0.0):
         self.device = torch.device(device)
         self.model = model
         self.dp_group = group
@@ -47,6 +47,7 @@ class DataParallelEngine(Engine):
             from ..ops.amp import GradScaler
 
             self.scaler = GradScaler(self.device)
+        self._make_clipper(max_grad_norm)
         # HIP-graph "compile": at one rank, or across ranks when the gradient all-reduces ride
         # the capturable native RCCL transport
         tp = getattr(self.store, "tp", None)
@@ -64,14 +65,24 @@ class DataParallelEngine(Engine):
             return self._optim(out)
 
     def _optim(self, out):
-        if self.scaler is not None:
-            # the non-finite check needs every bucket reduced before any parameter moves;
-            # all-reduced gradients are identical on every rank, so is the flag
+        if self.scaler is not None or self.clipper is not None:
+            # the non-finite check and the global norm need every bucket reduced before any
+            # parameter moves; all-reduced gradients are identical on every rank, so are the flag
+            # and the norm (its sum has a fixed order: ops/clip.py) -- no collective for either
             if isinstance(self.store, DDPStore):
                 self.store.finish_grads()
-            self.scaler.check(self.store.grads)
-            self.opt.step(grad_scale=1.0 / self.dp_world, **self.scaler.opt_kwargs(self.opt))
-            self.scaler.update()
+            kw = {}
+            if self.scaler is not None:
+                self.scaler.check(self.store.grads)
+                kw = self.scaler.opt_kwargs(self.opt)
+            if self.clipper is not None:
+                cl = self.clipper
+                cl.begin()
+                cl.add(self.store.grads, replicated=True)
+                kw.update(cl.finish(1.0 / self.dp_world, kw.get("grad_scale_t")))
+            self.opt.step(grad_scale=1.0 / self.dp_world, **kw)
+            if self.scaler is not None:
+                self.scaler.update()
             return out.loss.detach()
         if isinstance(self.store, DDPStore) and self.store.tp.active and self.store.master.is_cuda:
             # bucket by bucket: AdamW of the buckets already reduced runs on the compute stream

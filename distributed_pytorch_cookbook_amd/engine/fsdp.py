@@ -30,7 +30,7 @@ class FSDPEngine(Engine):
     def __init__(self, model, device, lr: float, group=None, prefetch: int = 1,
                  reshard_after_forward: bool = True, cpu_offload: bool = False, compute_dtype=None,
                  reduce_dtype=torch.float32, grad_scaler: bool = False, graph: bool = False,
-                 comm_kind: str | None = None, force_sharded: bool = False):
+                 comm_kind: str | None = None, force_sharded: bool = False, max_grad_norm: float = 0.0):
         self.device = torch.device(device)
         self.model = model
         self.dp_group = group
@@ -49,6 +49,7 @@ class FSDPEngine(Engine):
             from ..ops.amp import GradScaler
 
             self.scaler = GradScaler(self.device)
+        self._make_clipper(max_grad_norm)
         # HIP-graph "compile" of the whole sharded step (gathers, reduce-scatters, AdamW);
         # not with --cpu_offload, whose optimizer runs on the host
         self.graph = (graph and self.device.type == "cuda" and not st.cpu_offload
@@ -67,9 +68,10 @@ class FSDPEngine(Engine):
             out = self.model(**batch, targets=targets)
         with mark("bwd"):  # (re-gathers and reduce-scatters enqueued inside)
             self._scaled(out.loss).backward()
-        if self.scaler is None and not st.cpu_offload and st.sharded and st.tp.active:
+        if self.scaler is None and self.clipper is None and not st.cpu_offload and st.sharded and st.tp.active:
             # unit by unit: AdamW of the units already reduce-scattered on the compute stream
-            # while the remaining reduce-scatters are still on the comm stream
+            # while the remaining reduce-scatters are still on the comm stream (not with the
+            # scaler or clipping: both need every gradient before any parameter moves)
             with mark("optim"):
                 st.finish_grads_and_update(self.opt, self.opt_rep, grad_scale=1.0 / self.dp_world)
             return out.loss.detach()
@@ -80,26 +82,44 @@ class FSDPEngine(Engine):
 
     def _optim(self, out):
         st = self.store
-        if st.cpu_offload and self.scaler is None and not _OFFLOAD_SYNC:
+        cl = self.clipper
+        if st.cpu_offload and self.scaler is None and cl is None and not _OFFLOAD_SYNC:
             # pipelined host AdamW: overlaps the next step's forward (FSDPStore.host_step)
             st.host_step(self.opt, grad_scale=1.0 / self.dp_world)
             self.opt_rep.step(grad_scale=1.0 / self.dp_world)
             return out.loss.detach()
+        if cl is not None:
+            # on the device gradients, before any D2H copy of --cpu_offload.  The shards differ
+            # per rank (summed over the group); the replicated 1-D gradients were all-reduced by
+            # finish_grads and are counted once.  The whole of st.grads is summed: its padding
+            # (units are padded to W x 64 elements) and the slots of the 1-D parameters inside the
+            # units are zero here -- zero_grad clears the buffer, the unit gradient buffers start
+            # as zeros, the kernels write parameter views only and the 1-D gradients live in
+            # rep_grads -- found zero, so nothing is excluded (tests/test_grad_clip_cpu.py checks
+            # the norm against the unsharded engine's)
+            cl.begin()
+            cl.add(st.grads, replicated=False)
+            cl.add(st.rep_grads, replicated=True)
+            if st.sharded:
+                cl.reduce(st.tp)
         if st.cpu_offload:
             st.grads_host.copy_(st.grads, non_blocking=True)
             torch.cuda.current_stream().synchronize()  # grads_host D2H landed
+        kw, kw_rep = {}, {}
         if self.scaler is not None:
             # shards differ per rank: the skip decision is reduced over the group
             sc = self.scaler
             sc.check(self.opt.grad)
             sc.check(self.opt_rep.grad)
             sc.reduce_flag(self.dp_group)
-            self.opt.step(grad_scale=1.0 / self.dp_world, **sc.opt_kwargs(self.opt))
-            self.opt_rep.step(grad_scale=1.0 / self.dp_world, **sc.opt_kwargs(self.opt_rep))
-            sc.update()
-            return out.loss.detach()
-        self.opt.step(grad_scale=1.0 / self.dp_world)
-        self.opt_rep.step(grad_scale=1.0 / self.dp_world)
+            kw, kw_rep = sc.opt_kwargs(self.opt), sc.opt_kwargs(self.opt_rep)
+        if cl is not None:
+            cl.finish(1.0 / self.dp_world, None if self.scaler is None else self.scaler.inv_scale_t)
+            kw, kw_rep = {**kw, **cl.opt_kwargs(self.opt)}, {**kw_rep, **cl.opt_kwargs(self.opt_rep)}
+        self.opt.step(grad_scale=1.0 / self.dp_world, **kw)
+        self.opt_rep.step(grad_scale=1.0 / self.dp_world, **kw_rep)
+        if self.scaler is not None:
+            self.scaler.update()
         return out.loss.detach()
 
     @torch.no_grad()

@@ -45,9 +45,10 @@ class PipelineEngine(Engine):
                  schedule: str = "1f1b", bucket_mb: float = 128.0, compute_dtype=None,
                  seq_len: int | None = None, grad_scaler: bool = False, comm_kind: str | None = None,
                  wire_dtype=None, graph: bool = False, force_dist: bool = False,
-                 reduce_dtype=torch.float32):
+                 reduce_dtype=torch.float32, max_grad_norm: float = 0.0):
         self.device = torch.device(device)
         self.model = model
+        self._make_clipper(max_grad_norm)
         if grad_scaler:
             from ..ops.amp import GradScaler
 
@@ -226,7 +227,7 @@ class PipelineEngine(Engine):
             order = (schedule_gpipe if self.schedule == "gpipe" else schedule_1f1b)(self.n_micro, self.stage, self.pp)
         run_schedule(order, self.first, self.last, forward, backward, self.p2p, shape, wgrad=wgrad)
         assert not wq, "zero-bubble schedule left weight gradients unrun"
-        if isinstance(st, DDPStore) and st.tp.active and self.scaler is None:
+        if isinstance(st, DDPStore) and st.tp.active and self.scaler is None and self.clipper is None:
             # bucket by bucket, as the DDP engine does: AdamW of the buckets whose replica
             # all-reduce has landed runs while the later ones are still on the links (a stage's
             # buckets launch from its last micro-batch's backward -- or W -- passes, unit by unit)
@@ -255,14 +256,24 @@ class PipelineEngine(Engine):
         return self._cost_cache[key]
 
     def _optim(self, acc):
+        kw = {}
         if self.scaler is not None:
             # every stage holds different gradients: one skip decision for the whole job
             self.scaler.check(self.opt.grad)
             self.scaler.reduce_flag(None)
-            self.opt.step(grad_scale=1.0 / self.dp, **self.scaler.opt_kwargs(self.opt))
+            kw = self.scaler.opt_kwargs(self.opt)
+        if self.clipper is not None:
+            # the stages hold disjoint units (no weight is tied across stages), so the global norm
+            # sums the stages' squares over the pipeline group; with PP x DP the replica
+            # all-reduce has already made a stage's gradients identical across its replicas
+            cl = self.clipper
+            cl.begin()
+            cl.add(self.opt.grad, replicated=False)
+            cl.reduce(self.pp_tp)
+            kw.update(cl.finish(1.0 / self.dp, kw.get("grad_scale_t")))
+        self.opt.step(grad_scale=1.0 / self.dp, **kw)
+        if self.scaler is not None:
             self.scaler.update()
-            return acc.get("loss")
-        self.opt.step(grad_scale=1.0 / self.dp)
         return acc.get("loss")
 
     @torch.no_grad()

@@ -239,6 +239,10 @@ class Trainer:
                 rec = {"epoch": ei + 1, "step": e.step_count, "loss": avg, "tokens_per_s": tps,
                        "tokens_per_s_per_gpu": tps / max(comm.world_size(), 1), "mfu": util,
                        "step_ms": 1000.0 * dt / PRINT_FREQ, "peak_mem_gib": peak_memory_gib(self.device)}
+                if e.grad_norm is not None:
+                    # --max_grad_norm: the last step's norm before clipping (read here, where the
+                    # loop has just synchronised)
+                    rec["grad_norm"] = float(e.grad_norm)
                 self.history.append(rec)
                 self._jsonl(rec)
                 window, nwin, tokens, t0 = None, 0, 0, time.perf_counter()

@@ -142,6 +142,24 @@ class AmpUpdateArgs(ctypes.Structure):
                 ("growth", c_float), ("backoff", c_float), ("interval", c_int)]
 
 
+class GradSumsqArgs(ctypes.Structure):
+    """``misc.hip:GradSumsqArgs``."""
+    _fields_ = [("g", P), ("n", LL), ("partials", P), ("sumsq", P), ("slot", c_int)]
+
+
+class ClipCoefArgs(ctypes.Structure):
+    """``misc.hip:ClipCoefArgs``."""
+    _fields_ = [("sumsq", P), ("pre_scale_ptr", P), ("norm", P), ("coef", P), ("scale", P),
+                ("max_norm", c_float), ("pre_scale", c_float)]
+
+
+# geometry of ``dpc_grad_sumsq`` (misc.hip: SUMSQ_MAX_BLOCKS, SUMSQ_TRIP; checked at load): the
+# grid cap -- also the length of the partials buffer -- and the elements one trip of the whole
+# grid covers (blocks x 256 threads x 4 vectors x 4 floats)
+SUMSQ_MAX_BLOCKS = 1024
+SUMSQ_TRIP = SUMSQ_MAX_BLOCKS * 256 * 4 * 4
+
+
 class CastArgs(ctypes.Structure):
     _fields_ = [("src", P), ("dst", P), ("n", LL)]
 
@@ -212,6 +230,8 @@ _FUNCS = {
     "dpc_adamw": AdamArgs,
     "dpc_amp_check": AmpCheckArgs,
     "dpc_amp_update": AmpUpdateArgs,
+    "dpc_grad_sumsq": GradSumsqArgs,
+    "dpc_clip_coef": ClipCoefArgs,
     "dpc_cast_f32_bf16": CastArgs,
     "dpc_bias_act_bwd": BiasActArgs,
     "dpc_dropout_residual": DropResArgs,
@@ -260,6 +280,12 @@ def lib() -> ctypes.CDLL:
             handle.dpc_occupy.restype = c_int
             handle.dpc_embedding_bwd_ws.argtypes = [c_int, c_int]
             handle.dpc_embedding_bwd_ws.restype = ctypes.c_ulonglong
+            handle.dpc_grad_sumsq_max_blocks.argtypes = []
+            handle.dpc_grad_sumsq_max_blocks.restype = c_int
+            handle.dpc_grad_sumsq_trip.argtypes = []
+            handle.dpc_grad_sumsq_trip.restype = ctypes.c_longlong
+            if (handle.dpc_grad_sumsq_max_blocks(), handle.dpc_grad_sumsq_trip()) != (SUMSQ_MAX_BLOCKS, SUMSQ_TRIP):
+                raise RuntimeError("kernel library: dpc_grad_sumsq geometry differs from ops/_lib.py")
             # intra-node peer-access collectives (ipc_coll.hip, parallel/ipc_comm.py)
             handle.dpc_ipc_alloc.argtypes = [ctypes.c_longlong, c_int, ctypes.POINTER(c_void_p)]
             handle.dpc_ipc_free.argtypes = [c_void_p]

@@ -66,6 +66,7 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
     # never under --coll_check, whose fingerprints are host-synchronous collectives
     graph = (not args.disable_compile and not args.disable_amp
              and not getattr(args, "coll_check", False))
+    max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
     if recipe in ("single", "ddp"):
         from .engine.data_parallel import DataParallelEngine
 
@@ -74,6 +75,7 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
             reduce_dtype=reduce_dtype,
             overlap=not args.no_overlap, compute_dtype=compute_dtype, graph=graph,
             comm_kind=comm_kind, grad_scaler=getattr(args, "grad_scaler", False), force_ddp_store=force_dist,
+            max_grad_norm=max_grad_norm,
         )
     if recipe == "fsdp":
         from .engine.fsdp import FSDPEngine
@@ -82,7 +84,7 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
                           reshard_after_forward=not args.no_reshard_after_forward,
                           cpu_offload=args.cpu_offload, compute_dtype=compute_dtype,
                           reduce_dtype=reduce_dtype, grad_scaler=getattr(args, "grad_scaler", False), graph=graph, comm_kind=comm_kind,
-                          force_sharded=force_dist)
+                          force_sharded=force_dist, max_grad_norm=max_grad_norm)
     if recipe in ("pipe", "pipe_ddp"):
         from .engine.pipeline import PipelineEngine
 
@@ -93,7 +95,7 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
                               schedule=args.schedule, bucket_mb=args.bucket_mb,
                               compute_dtype=compute_dtype, grad_scaler=getattr(args, "grad_scaler", False),
                               comm_kind=comm_kind, wire_dtype=wire, graph=graph, force_dist=force_dist,
-                              reduce_dtype=reduce_dtype)
+                              reduce_dtype=reduce_dtype, max_grad_norm=max_grad_norm)
     raise ValueError(recipe)
 
 
