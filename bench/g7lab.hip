@@ -156,7 +156,6 @@ int main(int argc, char** argv) {
     vs.push_back({"s6", [&] { launch<0, AK_, BK_, 6>(a, pl, ab, bb); }, false, {}});                      \
   } else {                                                                                                \
     vs.push_back({"s3", [&] { launch<0, AK_, BK_>(a, pl, ab, bb); }, false, {}});                         \
-    vs.push_back({"s3_old", [&] { launch<256, AK_, BK_>(a, pl, ab, bb); }, false, {}});                   \
     vs.push_back({"s6", [&] { launch<0, AK_, BK_, 6>(a, pl, ab, bb); }, false, {}});                      \
     vs.push_back({"s3_clk", [&] { launch<128, AK_, BK_>(a, pl, ab, bb); }, true, {}});                    \
     vs.push_back({"s6_clk", [&] { launch<128, AK_, BK_, 6>(a, pl, ab, bb); }, true, {}});                 \

@@ -401,27 +401,23 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(GemmArgs p) {
 
 
 
-template <int NL>
-__device__ __forceinline__ void issue_tile(const void* base, unsigned long long total, unsigned long long off,
-                                           const int* voff, bf16_t* lds_tile, int wave) {
-  // descriptor whose base is `off` bytes into the operand and whose range ends with it
-  const unsigned long long left = off < total ? total - off : 0ull;
-  const unsigned nrec = left > 0xffffffffull ? 0xffffffffu : (unsigned)left;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + off), 0, nrec, 0x00020000);
-#pragma unroll
-  for (int i = 0; i < NL; ++i) {
-    const int j = wave * NL + i;  // wave-instruction index: 1 KiB of the tile
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t)(lds_tile + j * 512), 16, voff[i], 0, 0, 0);
-  }
-}
-
 // buffer descriptor whose base is `off` bytes into the operand and whose range ends with it
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, unsigned long long total,
                                                             unsigned long long off) {
   const unsigned long long left = off < total ? total - off : 0ull;
   const unsigned nrec = left > 0xffffffffull ? 0xffffffffu : (unsigned)left;
   return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + off), 0, nrec, 0x00020000);
+}
+
+template <int NL>
+__device__ __forceinline__ void issue_tile(const void* base, unsigned long long total, unsigned long long off,
+                                           const int* voff, bf16_t* lds_tile, int wave) {
+  const __amdgpu_buffer_rsrc_t rs = make_rsrc(base, total, off);
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {
+    const int j = wave * NL + i;  // wave-instruction index: 1 KiB of the tile
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t)(lds_tile + j * 512), 16, voff[i], 0, 0, 0);
+  }
 }
 
 
@@ -629,6 +625,62 @@ __global__ __launch_bounds__((V3Cfg<BM_, BN_, WM, WN, KB, STAGES>::NTH), (V3Cfg<
   epi_tile<FM, (FM == 4 && Cfg::WGS == 1)>(p, acc, reinterpret_cast<float*>(smem) + wid * 32 * 64, splits, m0 + wr * Cfg::WTM, n0 + wc * 64, lane);
 }
 
+// ---- the reduction passes behind the persistent kernels (gemm_run launches them)
+// colsum[n] += sum over the R rows of ws [R][N] (g7_epilogue_act_lds's per-tile partial column
+// sums): 4 columns per thread, 16 rows per workgroup row (grid.y), one atomic per column per 16
+// rows
+static __global__ __launch_bounds__(256) void g7_colsum_reduce(float* colsum, const float* ws, int R, int N) {
+  const int c4 = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (c4 >= N) return;
+  const int r0 = blockIdx.y * 16, r1 = min(R, r0 + 16);
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 16
+  for (int r = r0; r < r1; ++r) {
+    const float4 v = *reinterpret_cast<const float4*>(ws + (long long)r * N + c4);
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  atomicAdd(colsum + c4, s.x);
+  atomicAdd(colsum + c4 + 1, s.y);
+  atomicAdd(colsum + c4 + 2, s.z);
+  atomicAdd(colsum + c4 + 3, s.w);
+}
+
+// C (=, or += when accumulating) the sum of the s workspace slabs [s][M][N]; 4 columns per
+// thread (N % 8 == 0, ldc % 8 == 0: 16-B rows)
+static __global__ __launch_bounds__(256) void g7_splitk_reduce(float* C, long long ldc, const float* ws, int M, int N,
+                                                       int s, int accumulate, int nt = 0) {
+  const long long nq = (long long)M * (N >> 2);
+  const long long slab = (long long)M * N;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nq; i += (long long)gridDim.x * 256) {
+    const long long m = i / (N >> 2), n = (i - m * (N >> 2)) << 2;
+    const float* w = ws + m * N + n;
+    float4 v = *reinterpret_cast<const float4*>(w);
+    // four slabs' loads in flight before their adds (the one-at-a-time loop waited for each:
+    // 2.9 TB/s), the adds in the same order as before (bitwise the same sums)
+    int k = 1;
+    for (; k + 3 < s; k += 4) {
+      const float4 u0 = *reinterpret_cast<const float4*>(w + k * slab);
+      const float4 u1 = *reinterpret_cast<const float4*>(w + (k + 1) * slab);
+      const float4 u2 = *reinterpret_cast<const float4*>(w + (k + 2) * slab);
+      const float4 u3 = *reinterpret_cast<const float4*>(w + (k + 3) * slab);
+      v.x += u0.x; v.y += u0.y; v.z += u0.z; v.w += u0.w;
+      v.x += u1.x; v.y += u1.y; v.z += u1.z; v.w += u1.w;
+      v.x += u2.x; v.y += u2.y; v.z += u2.z; v.w += u2.w;
+      v.x += u3.x; v.y += u3.y; v.z += u3.z; v.w += u3.w;
+    }
+    for (; k < s; ++k) {
+      const float4 u = *reinterpret_cast<const float4*>(w + k * slab);
+      v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+    }
+    float4* c = reinterpret_cast<float4*>(C + m * ldc + n);
+    if (accumulate) {
+      const float4 o = *c;
+      v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
+    }
+    st16(c, v, nt);
+  }
+}
+
 // (v5, the 256x256 eight-wave ping-pong kernel, was removed in round 5: no tuned-table entry and
 // no policy branch chose it once v7 took the weight gradients)
 
@@ -640,37 +692,8 @@ using namespace dpc;
 // split-K plan, reduction passes: a pure function, pinned on the CPU by
 // tests/test_gemm_plan_cpu.py); gemm_run below launches what a plan says and decides nothing.
 //
-// The persistent family (v7 / v8 / v7d: gemm7_kern.h, v9: gemm9_kern.h) -- why its shape
-// (MI355X, measured with bench/gemm_ab.py): the 8-wave ping-pong kernels it replaced paid two
-// workgroup barriers per 16 MFMAs and re-read 12 fragments per 32 MFMAs; on short-K products
-// (K = 768: the QKV / out / up / LM-head forward products of GPT-2 small) they also drained the
-// whole pipeline at every tile -- prologue latency + a 128 KiB store burst per CU with the matrix
-// pipe idle -- and ran at ~680 TF/s against hipBLASLt's ~1,200.  Here:
-//   * each wave owns a 128x128 output tile: 8 x 8 accumulators of v_mfma_f32_16x16x32_bf16
-//     (256 accumulator registers; a 512-register wave, one per SIMD), i.e. 16 fragment reads
-//     per 64 MFMAs (0.25 / MFMA vs 0.375) and ONE workgroup barrier per 32-deep k-slice
-//     (1,024 MFMA cycles per SIMD);
-//   * the k-slices of all the tiles a workgroup owns form one stream: an NS-slot LDS ring
-//     (32 KiB per slot: A 256x32 + B 256x32) filled by LDS-DMA (buffer_load ... lds) DIST =
-//     NS-1 slices ahead, never drained at a tile boundary, so the next tile's first slices are
-//     in flight while the previous tile's epilogue runs;
-//   * fragments of slice q+1 are read into a second register set while the MFMAs of slice q
-//     run (two named sets, the loop unrolled by two);
-//   * the MFMA operands are swapped (C^T = B A^T): lane l of a 16x16 accumulator holds output
-//     row l & 15 and four CONSECUTIVE columns 4 (l >> 4) + r, so the epilogue works straight
-//     from registers -- no LDS staging, no barrier: 16-B f32 stores, and for bf16 outputs
-//     v_permlane16_swap pairs two fragments' 8-B halves into one 16-B store per lane.
-// LDS images and fragment reads are the v3 ones (gemm.h): k-major [rows][32] with the 16-B
-// chunk swizzle, mn-major [k][128-column halves] read with ds_read_b64_tr_b16.
-//
-// Synchronisation (per slice q, every wave):  body(q) = MFMAs on frags(q) | reads of frags(q+1)
-// from slot (q+1) % NS | DMA of slice q+DIST into slot (q+DIST) % NS | epilogue if q ends a
-// tile;  then vmcnt(slice q+2 landed) + s_barrier.
-//   RAW: slot (q+2) is read in body(q+1), after this barrier, which every wave enters after its
-//        own counted vmcnt for slice q+2 (its DMA pieces are older than the count).
-//   WAR: slot (q+DIST) % NS held slice q-1, read in body(q-2) and consumed by the MFMAs of
-//        body(q-1), i.e. retired before every wave passed barrier(q-1) -- before any wave
-//        can be in body(q).
+// The persistent family's design and synchronisation notes: the top of gemm7_kern.h (v7 / v8 /
+// v7d) and of gemm9_kern.h (v9).
 static_assert(GP_ACT_GELU == ACT_GELU && GP_ACT_MUL == ACT_MUL && GP_G7_KB == G7_KB && G_SP_DEFAULT == 3,
               "gemm_plan.h's copies of the kernels' constants");
 
@@ -695,7 +718,6 @@ static GemmSettings& settings() {
     s.nt_store = env_int("DPC_GEMM_NT", s.nt_store);
     s.act_lds_env = env_int("DPC_G7_ACTLDS", 1);
     s.res_lds_env = env_int("DPC_G7_RESLDS", 1);
-    s.debug = env_int("DPC_G7_DEBUG", 0);
     s.cus = 0;  // asked of the device by the first product (settings_for_launch)
     return s;
   }();

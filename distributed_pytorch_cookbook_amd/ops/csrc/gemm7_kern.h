@@ -1,6 +1,40 @@
-// Device side of the persistent v7 / v8 / v7d GEMM kernels (host dispatch: gemm7.hip; the
-// design notes are at the top of gemm7.hip).  A header so that bench/g7lab.hip can build
-// single instantiations of the kernels for ablations and A/B runs in seconds.
+// Device side of the persistent v7 / v8 / v7d GEMM kernels (v9: gemm9_kern.h, which builds on
+// this file).  gemm_plan.h decides which instantiation a product gets, gemm.hip launches it, the
+// gemm7_part*.hip files compile the instantiations of gemm_parts.txt.  A header so that
+// bench/g7lab.hip can build single instantiations of the kernels for ablations and A/B runs in
+// seconds.
+//
+// Why the family has its shape (MI355X, measured with bench/gemm_ab.py): the 8-wave ping-pong
+// kernels it replaced paid two
+// workgroup barriers per 16 MFMAs and re-read 12 fragments per 32 MFMAs; on short-K products
+// (K = 768: the QKV / out / up / LM-head forward products of GPT-2 small) they also drained the
+// whole pipeline at every tile -- prologue latency + a 128 KiB store burst per CU with the matrix
+// pipe idle -- and ran at ~680 TF/s against hipBLASLt's ~1,200.  Here:
+//   * each wave owns a 128x128 output tile: 8 x 8 accumulators of v_mfma_f32_16x16x32_bf16
+//     (256 accumulator registers; a 512-register wave, one per SIMD), i.e. 16 fragment reads
+//     per 64 MFMAs (0.25 / MFMA vs 0.375) and ONE workgroup barrier per 32-deep k-slice
+//     (1,024 MFMA cycles per SIMD);
+//   * the k-slices of all the tiles a workgroup owns form one stream: an NS-slot LDS ring
+//     (32 KiB per slot: A 256x32 + B 256x32) filled by LDS-DMA (buffer_load ... lds) DIST =
+//     NS-1 slices ahead, never drained at a tile boundary, so the next tile's first slices are
+//     in flight while the previous tile's epilogue runs;
+//   * fragments of slice q+1 are read into a second register set while the MFMAs of slice q
+//     run (two named sets, the loop unrolled by two);
+//   * the MFMA operands are swapped (C^T = B A^T): lane l of a 16x16 accumulator holds output
+//     row l & 15 and four CONSECUTIVE columns 4 (l >> 4) + r, so the epilogue works straight
+//     from registers -- no LDS staging, no barrier: 16-B f32 stores, and for bf16 outputs
+//     v_permlane16_swap pairs two fragments' 8-B halves into one 16-B store per lane.
+// LDS images and fragment reads are the v3 ones (gemm.h): k-major [rows][32] with the 16-B
+// chunk swizzle, mn-major [k][128-column halves] read with ds_read_b64_tr_b16.
+//
+// Synchronisation (per slice q, every wave):  body(q) = MFMAs on frags(q) | reads of frags(q+1)
+// from slot (q+1) % NS | DMA of slice q+DIST into slot (q+DIST) % NS | epilogue if q ends a
+// tile;  then vmcnt(slice q+2 landed) + s_barrier.
+//   RAW: slot (q+2) is read in body(q+1), after this barrier, which every wave enters after its
+//        own counted vmcnt for slice q+2 (its DMA pieces are older than the count).
+//   WAR: slot (q+DIST) % NS held slice q-1, read in body(q-2) and consumed by the MFMAs of
+//        body(q-1), i.e. retired before every wave passed barrier(q-1) -- before any wave
+//        can be in body(q).
 #pragma once
 #include "gemm.h"
 
@@ -37,7 +71,7 @@ __device__ __forceinline__ void g7_tile(const G7Plan& pl, int u, int& m0, int& n
 // s_waitcnt vmcnt(0) in front of every later ds_read_b64_tr_b16 (the transposing read of the
 // mn-major images), which drained the whole prefetch ring once per fragment and held the
 // B-n-major / weight-gradient layouts at ~380 TF/s.  Hidden in asm the DMA is ordered only by
-// this kernel's own counted vmcnt + barrier (see the synchronisation notes above); the compiler
+// this kernel's own counted vmcnt + barrier (the synchronisation notes at the top of this file); the compiler
 // never counts these loads, so every vmcnt it emits for its own loads over-waits (safe).
 // M0 (the LDS destination base) is saved and restored around the piece.
 __device__ __forceinline__ void g7_piece(__amdgpu_buffer_rsrc_t rs, int voff, const bf16_t* lds) {
@@ -139,15 +173,48 @@ __device__ __forceinline__ float g7_alpha(const GemmArgs& p) {
   return a;
 }
 
-#ifndef G7_EPI_PF
-#define G7_EPI_PF 0  // 0 = the default depth per epilogue (A/B builds override)
-#endif
-
 // lane l <- lane l ^ 8 within each 16-lane row (DPP row_ror:8, a VALU op)
 __device__ __forceinline__ unsigned g7_ror8(unsigned v) {
   return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false);
 }
 __device__ __forceinline__ float g7_ror8(float v) { return __uint_as_float(g7_ror8(__float_as_uint(v))); }
+
+// Whole-line stores from the register layout: lanes l and l ^ 8 of a 16-lane row (output rows r
+// and r + 8) hold the 16-B chunks c0, c1 of two column blocks and trade one through a DPP row
+// rotate -- out come dA (row r & 7: both chunks of its first block's line) and dB (row (r & 7)
+// + 8), so that one store instruction covers 8 rows x 128 B.  V: uint4 (bf16) or float4.
+// (g7_split_store keeps its own copy of these four lines: calling this there changed the v7d
+// kernels' register allocation.)
+template <typename V>
+__device__ __forceinline__ void g7_line_exchange(bool lo, const V& c0, const V& c1, V& dA, V& dB) {
+  const V snd{lo ? c1.x : c0.x, lo ? c1.y : c0.y, lo ? c1.z : c0.z, lo ? c1.w : c0.w};
+  const V rcv{g7_ror8(snd.x), g7_ror8(snd.y), g7_ror8(snd.z), g7_ror8(snd.w)};
+  dA = V{lo ? c0.x : rcv.x, lo ? c0.y : rcv.y, lo ? c0.z : rcv.z, lo ? c0.w : rcv.w};
+  dB = V{lo ? rcv.x : c1.x, lo ? rcv.y : c1.y, lo ? rcv.z : c1.z, lo ? rcv.w : c1.w};
+}
+
+// ---- pieces of the LDS-staged epilogues (g7_epilogue_act_lds, g7_epilogue_res_lds)
+// every wave's reads of a staging buffer retired -> it may be refilled
+__device__ __forceinline__ void g7_reads_done() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// a part's DMA landed (every wave's): younger vector-memory ops = the previous part's ST stores
+// per lane (st; every tile issues all of them -- out-of-range ones are dropped by their
+// descriptor, still counted) + the next part's 8 DMA pieces when one was issued (next)
+template <int ST>
+__device__ __forceinline__ void g7_landed(bool st, bool next) {
+  if (st) {
+    if (next) g7_wait<ST + 8>();
+    else g7_wait<ST>();
+  } else {
+    if (next) g7_wait<8>();
+    else g7_wait<0>();
+  }
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
 
 // PK: GELU / GELU' in packed-f32 math (v8 with a K-major A, v7's forward epilogues)
 // NOLD: MODE 1 known at compile time to read nothing per element (no residual / accumulate --
@@ -165,6 +232,8 @@ __device__ __forceinline__ float g7_ror8(float v) { return __uint_as_float(g7_ro
 // SP (MODE 1): the bf16 stores' cache policy at compile time (st16p pol; -1 = GemmArgs::nt_store at
 // run time).  The run-time policy is a 4-way switch in front of EVERY store of the unrolled
 // epilogue -- ~2 scalar branches per 16-B store in the round-6 asm of the v9 forward epilogue.
+// dbg (MODE 0, bench/g7lab.hip's arms): 4 = the epilogue's VALU without its stores, 16 = non-temporal
+// bf16 stores whatever GemmArgs::nt_store says.  A constant 0 at every call but v8's, see there.
 template <int MODE, int NJ, bool PK = false, bool NOLD = false, int FA = -1, bool FULL = false, bool AD = false,
           int SP = -1>
 __device__ __forceinline__ void g7_epilogue(const GemmArgs& p, floatx4 (&acc)[8][NJ], int mw, int nw, int lane,
@@ -196,10 +265,8 @@ __device__ __forceinline__ void g7_epilogue(const GemmArgs& p, floatx4 (&acc)[8]
           asm volatile("" : "+v"(a0), "+v"(a1));
           float4 c0 = make_float4(a0[0] * alpha, a0[1] * alpha, a0[2] * alpha, a0[3] * alpha);
           float4 c1 = make_float4(a1[0] * alpha, a1[1] * alpha, a1[2] * alpha, a1[3] * alpha);
-          const float4 snd = make_float4(lo ? c1.x : c0.x, lo ? c1.y : c0.y, lo ? c1.z : c0.z, lo ? c1.w : c0.w);
-          const float4 rcv = make_float4(g7_ror8(snd.x), g7_ror8(snd.y), g7_ror8(snd.z), g7_ror8(snd.w));
-          const float4 dA = make_float4(lo ? c0.x : rcv.x, lo ? c0.y : rcv.y, lo ? c0.z : rcv.z, lo ? c0.w : rcv.w);
-          const float4 dB = make_float4(lo ? rcv.x : c1.x, lo ? rcv.y : c1.y, lo ? rcv.z : c1.z, lo ? rcv.w : c1.w);
+          float4 dA, dB;
+          g7_line_exchange(lo, c0, c1, dA, dB);
           const int m = mw + 16 * i + rr, n = nw + 16 * j + 4 * g + 16 * hi8;
           if (n < p.N) {
             float* C = static_cast<float*>(p.C) + (long long)m * p.ldc + n;
@@ -232,17 +299,14 @@ __device__ __forceinline__ void g7_epilogue(const GemmArgs& p, floatx4 (&acc)[8]
           c0 = make_uint4(s0[0], s1[0], s0[1], s1[1]);
           c1 = make_uint4(t0[0], t1[0], t0[1], t1[1]);
         }
-        const uint4 snd = make_uint4(lo ? c1.x : c0.x, lo ? c1.y : c0.y, lo ? c1.z : c0.z, lo ? c1.w : c0.w);
-        const uint4 rcv = make_uint4(g7_ror8(snd.x), g7_ror8(snd.y), g7_ror8(snd.z), g7_ror8(snd.w));
-        const uint4 dA = make_uint4(lo ? c0.x : rcv.x, lo ? c0.y : rcv.y, lo ? c0.z : rcv.z, lo ? c0.w : rcv.w);
-        const uint4 dB = make_uint4(lo ? rcv.x : c1.x, lo ? rcv.y : c1.y, lo ? rcv.z : c1.z, lo ? rcv.w : c1.w);
+        uint4 dA, dB;
+        g7_line_exchange(lo, c0, c1, dA, dB);
         const int m = mw + 16 * i + rr, n = nw + 16 * j + coff + 32 * hi8;
-        if ((dbg & 4) || ((dbg & 8) && (blockIdx.x & 1))) {  // (experiments: the epilogue's VALU
-          // without its stores -- on every workgroup (4) or on every other one (8))
+        if (dbg & 4) {
           asm volatile("" ::"v"(dA.x), "v"(dA.y), "v"(dA.z), "v"(dA.w), "v"(dB.x), "v"(dB.y), "v"(dB.z), "v"(dB.w));
         } else if (n < p.N) {
           bf16_t* C = static_cast<bf16_t*>(p.C) + (long long)m * p.ldc + n;
-          const bool nt = (p.nt_store & 1) || (dbg & 16);  // (dbg 16: the lab's nt arm)
+          const bool nt = (p.nt_store & 1) || (dbg & 16);
           if (m < p.M) st16p(C, dA, nt, (p.nt_store >> 2) & 3);
           if (m + 8 < p.M) st16p(C + 8 * p.ldc, dB, nt, (p.nt_store >> 2) & 3);
         }
@@ -276,7 +340,7 @@ __device__ __forceinline__ void g7_epilogue(const GemmArgs& p, floatx4 (&acc)[8]
   };
   // PF row blocks of operand reads in flight: the input-gradient epilogue's act' operand is an
   // 8-B read per lane and fragment, latency-bound at one block ahead
-  constexpr int PF = G7_EPI_PF > 0 ? G7_EPI_PF : (FWD || NJ > 4 ? 1 : 2);  // (v8; 3 - 4 spill there)
+  constexpr int PF = FWD || NJ > 4 ? 1 : 2;  // (v8; 3 - 4 spill there)
   uint4 ld[PF][NJ];
   float4 bias4[NJ];
   // (NOLD: the lane's bias column base as an LDS address)
@@ -546,40 +610,21 @@ __device__ __forceinline__ void g7_epilogue_act_lds(const GemmArgs& p, floatx4 (
       });
     });
   };
-  // wait until quarter q's pieces landed (every wave's): younger ops = the previous quarter's
-  // 8 stores (st; every tile issues all of them now -- out-of-range ones are dropped by the
-  // buffer descriptor, still counted) + the next quarter's DMA (8) when one was issued
-  auto landed = [&](bool st, bool next) G7_AI {
-    if (!next) {
-      if (st) g7_wait<8>();
-      else g7_wait<0>();
-    } else if (st) {
-      g7_wait<16>();
-    } else {
-      g7_wait<8>();
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  auto reads_done = [&]() G7_AI {  // every wave's reads of a buffer retired -> it may be refilled
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  reads_done();  // (the last body's fragment reads of the next tile's slice 0 -- buf1)
+  constexpr int ST = 8;  // stores per lane and quarter
+  g7_reads_done();  // (the last body's fragment reads of the next tile's slice 0 -- buf1)
   zdma(0, buf0);
   zdma(1, buf1);
-  landed(false, true);
+  g7_landed<ST>(false, true);
   proc(std::integral_constant<int, 0>{}, buf0);
-  reads_done();
+  g7_reads_done();
   zdma(2, buf0);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 1>{}, buf1);
-  reads_done();
+  g7_reads_done();
   zdma(3, buf1);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 2>{}, buf0);
-  landed(true, false);
+  g7_landed<ST>(true, false);
   proc(std::integral_constant<int, 3>{}, buf1);
   if (p.colsum) {
 #pragma unroll
@@ -602,7 +647,7 @@ __device__ __forceinline__ void g7_epilogue_act_lds(const GemmArgs& p, floatx4 (
       const int n = nw + 16 * (e >> 2) + 4 * g + (e & 3);
       if (n < p.N) {
         // the workspace form: this wave's partial column sums as row 2 (m0 / 256) + wr of a
-        // [2 tiles_m][N] f32 matrix (g7_colsum_reduce adds its rows into colsum) -- the f32
+        // [2 tiles_m][N] f32 matrix (g7_colsum_reduce, gemm.hip, adds its rows into colsum) -- the f32
         // atomics of every tile of a column block land on the same 256 addresses at nearly the
         // same time and serialise
         if (p.ws) static_cast<float*>(p.ws)[(long long)(2 * (m0 >> 8) + wr) * p.N + n] = v;
@@ -610,7 +655,7 @@ __device__ __forceinline__ void g7_epilogue_act_lds(const GemmArgs& p, floatx4 (
       }
     }
   }
-  reads_done();  // both buffers are ring slots again: the next tile's bodies 0 / 1 refill them
+  g7_reads_done();  // both buffers are ring slots again: the next tile's bodies 0 / 1 refill them
 }
 
 // MODE 1 with an f32 residual and an f32 output on v7 (the FFN down-projection forward: bias +
@@ -717,56 +762,39 @@ __device__ __forceinline__ void g7_epilogue_res_lds(const GemmArgs& p, floatx4 (
       __builtin_amdgcn_sched_barrier(0);
     });
   };
-  // eighth e landed: younger = eighth e-1's stores (8 f32 + 4 aux per lane: every tile issues
-  // all of them, out-of-range ones dropped by their descriptor) + the next DMA (8 pieces) when issued
-  auto landed = [&](bool st, bool next) G7_AI {
-    if (st) {
-      if (next) g7_wait<20>();
-      else g7_wait<12>();
-    } else {
-      if (next) g7_wait<8>();
-      else g7_wait<0>();
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  auto reads_done = [&]() G7_AI {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  reads_done();
+  constexpr int ST = 12;  // stores per lane and eighth: 8 f32 + 4 aux
+  g7_reads_done();
   rdma(0, buf0);
   rdma(1, buf1);
-  landed(false, true);
+  g7_landed<ST>(false, true);
   proc(std::integral_constant<int, 0>{}, buf0);
-  reads_done();
+  g7_reads_done();
   rdma(2, buf0);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 1>{}, buf1);
-  reads_done();
+  g7_reads_done();
   rdma(3, buf1);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 2>{}, buf0);
-  reads_done();
+  g7_reads_done();
   rdma(4, buf0);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 3>{}, buf1);
-  reads_done();
+  g7_reads_done();
   rdma(5, buf1);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 4>{}, buf0);
-  reads_done();
+  g7_reads_done();
   rdma(6, buf0);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 5>{}, buf1);
-  reads_done();
+  g7_reads_done();
   rdma(7, buf1);
-  landed(true, true);
+  g7_landed<ST>(true, true);
   proc(std::integral_constant<int, 6>{}, buf0);
-  landed(true, false);
+  g7_landed<ST>(true, false);
   proc(std::integral_constant<int, 7>{}, buf1);
-  reads_done();
+  g7_reads_done();
 }
 
 // split-K partial tile (non-swapped accumulators: lane l, register r of accumulator (i, j) holds
@@ -792,7 +820,7 @@ __device__ __forceinline__ void g7_epilogue_atomic(const GemmArgs& p, floatx4 (&
 
 // EPI: 0 = plain products (bf16 / f32 C), 1 = forward fused epilogues, 2 = split-K f32 atomics,
 // 3 = input-gradient fused epilogues (act', column sums), 4 = split-K partial tiles stored to
-// the workspace slab of their k-range (plain 16-B stores; g7_splitk_reduce sums the slabs),
+// the workspace slab of their k-range (plain 16-B stores; g7_splitk_reduce, gemm.hip, sums the slabs),
 // 8 = EPI 3 with an act' operand staged through LDS (v7 only; g7_epilogue_act_lds; 10 = the same
 // with act' precomputed, ACT_MUL), 9 = EPI 1
 // with an f32 residual and output, the residual staged through LDS (v7 only; g7_epilogue_res_lds).
@@ -802,9 +830,10 @@ __device__ __forceinline__ void g7_epilogue_atomic(const GemmArgs& p, floatx4 (&
 // and the store burst, which a lone wave per SIMD serialises against its MFMAs -- runs beside
 // the other's main loop).
 // ABL (bench/g7lab.hip only; every library instantiation has ABL = 0): main-loop ablations
-// that keep the instruction stream otherwise unchanged -- 16 = no workgroup barrier per slice,
-// 32 = no fragment reads (the prologue's fragments are reused), 64 = no counted vmcnt waits in
-// the loop, 128 = per-workgroup clock stamps into g7_clk (the in-kernel clock, DVFS check).
+// that keep the instruction stream otherwise unchanged -- 2 = no operand DMA, 16 = no workgroup
+// barrier per slice, 32 = no fragment reads (the prologue's fragments are reused), 128 =
+// per-workgroup clock stamps into g7_clk (the in-kernel clock, DVFS check); v9 adds 512 / 1024 /
+// 2048 (gemm9_kern.h).
 static __device__ unsigned long long g7_clk[2 * 2048];  // (per translation unit: lab only)
 
 template <int EPI, int SCHED, bool AK, bool BK, int WN = 128, int ABL = 0>
@@ -947,7 +976,6 @@ __global__ __launch_bounds__(256, WN == 128 ? 1 : 2) void gemm7_kernel(GemmArgs 
   // (measured on MI355X, bench/gemm_ab.py: 1 and 2 beat 0 by 2-6 %; all eight at the head
   // of the body or one at the tail of each group lost)
   auto piece_sched = [&](int g, bool tail) {
-    if ((ABL & 256) && (pl.debug & 2)) return;  // (the old runtime switch, A/B only)
     if (ABL & 2) return;
     if (SCHED == 0 && !tail && g < NP) piece(g);
 
@@ -966,9 +994,9 @@ __global__ __launch_bounds__(256, WN == 128 ? 1 : 2) void gemm7_kernel(GemmArgs 
   // the two fragment reads after MFMAs 0 and 1, and in the even groups the DMA pair's M0 write
   // and its two loads after MFMAs 2, 3 and 4; the next body's cursor (advance / prep) in group
   // 7 after MFMAs 1 and 4.  Every boundary pinned by sched_barrier.
-  auto mf = [&](int i, int j, const bf16x8* ac, const bf16x8* bcur, bool first) G7_AI {
-    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bcur[j], ac[i], first ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[i][j],
-                                                        0, 0, 0);
+  auto mf = [&](int i, int j, const bf16x8* ac, const bf16x8* bcur, bool first) G7_AI {  // (as G7_MFMA_ROW)
+    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(EPI == 2 ? ac[i] : bcur[j], EPI == 2 ? bcur[j] : ac[i],
+                                                        first ? floatx4{0.f, 0.f, 0.f, 0.f} : acc[i][j], 0, 0, 0);
   };
   auto dma5 = [&](int g, int step) G7_AI {  // step 0: M0, 1 / 2: the pair's loads
     if constexpr ((ABL & 2) != 0) return;
@@ -1030,8 +1058,7 @@ __global__ __launch_bounds__(256, WN == 128 ? 1 : 2) void gemm7_kernel(GemmArgs 
       __builtin_amdgcn_sched_barrier(0);                                                            \
     }                                                                                               \
     rd_slot = rd_slot + 1 == NS ? 0 : rd_slot + 1;                                                  \
-    if (ABL & 64) {                                                                                 \
-    } else if ((CREDIT || (ABL & 256)) && credit > 0) {                                             \
+    if ((CREDIT) && credit > 0) {                                                                   \
       --credit;                                                                                     \
       if (pl.store_cnt >= 48) g7_wait<(DIST - 2) * NP + 47>();                                      \
       else g7_wait<(DIST - 2) * NP + 31>();                                                         \
@@ -1065,7 +1092,7 @@ __global__ __launch_bounds__(256, WN == 128 ? 1 : 2) void gemm7_kernel(GemmArgs 
     const int uu = local + u * pl.grid;
     int m0, n0;
     g7_tile(pl, uu % ntiles, m0, n0);
-    if (pl.debug & 1) {
+    if (pl.debug & 1) {  // (bench/g7lab.hip's no_epilogue variants; the planner leaves 0)
     } else if constexpr (EPI == 2) {
       if constexpr (NJ == 8) g7_epilogue_atomic(p, acc, m0 + ar, n0 + bc, lane);
     } else if constexpr (EPI == 4) {
@@ -1075,7 +1102,10 @@ __global__ __launch_bounds__(256, WN == 128 ? 1 : 2) void gemm7_kernel(GemmArgs 
       q.out_f32 = 1;
       g7_epilogue<0, NJ>(q, acc, m0 + ar, n0 + bc, lane);
     } else if constexpr (EPI == 0) {
-      g7_epilogue<EPI, NJ, WN == 64 && AK>(p, acc, m0 + ar, n0 + bc, lane, pl.debug);
+      // (v7: no lab bits, the per-store tests fold away.  v8 keeps reading G7Plan::debug, always 0
+      // from the planner: with a constant, three of its seven kernels gained VGPR spills -- <0, 2,
+      // true, false, 64> 6 -> 9, <0, 2, false, true, 64> 8 -> 9, <0, 3, false, false, 64> 5 -> 6)
+      g7_epilogue<EPI, NJ, WN == 64 && AK>(p, acc, m0 + ar, n0 + bc, lane, WN == 64 ? pl.debug : 0);
     } else if constexpr (EPI == 9) {
       static_assert(WN == 128, "v7 only");
       // (ONE epilogue copy per v7 kernel: with act-specialised full-tile copies beside the
@@ -1112,61 +1142,6 @@ __global__ __launch_bounds__(256, WN == 128 ? 1 : 2) void gemm7_kernel(GemmArgs 
       g7_clk[2 * blockIdx.x] = t1 - clk_t0;
       g7_clk[2 * blockIdx.x + 1] = r1 - clk_r0;
     }
-  }
-}
-
-// colsum[n] += sum over the R rows of ws [R][N] (g7_epilogue_act_lds's per-tile partial column
-// sums): 4 columns per thread, 16 rows per workgroup row (grid.y), one atomic per column per 16
-// rows
-static __global__ __launch_bounds__(256) void g7_colsum_reduce(float* colsum, const float* ws, int R, int N) {
-  const int c4 = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (c4 >= N) return;
-  const int r0 = blockIdx.y * 16, r1 = min(R, r0 + 16);
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 16
-  for (int r = r0; r < r1; ++r) {
-    const float4 v = *reinterpret_cast<const float4*>(ws + (long long)r * N + c4);
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  atomicAdd(colsum + c4, s.x);
-  atomicAdd(colsum + c4 + 1, s.y);
-  atomicAdd(colsum + c4 + 2, s.z);
-  atomicAdd(colsum + c4 + 3, s.w);
-}
-
-// C (=, or += when accumulating) the sum of the s workspace slabs [s][M][N]; 4 columns per
-// thread (N % 8 == 0, ldc % 8 == 0: 16-B rows)
-static __global__ __launch_bounds__(256) void g7_splitk_reduce(float* C, long long ldc, const float* ws, int M, int N,
-                                                       int s, int accumulate, int nt = 0) {
-  const long long nq = (long long)M * (N >> 2);
-  const long long slab = (long long)M * N;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nq; i += (long long)gridDim.x * 256) {
-    const long long m = i / (N >> 2), n = (i - m * (N >> 2)) << 2;
-    const float* w = ws + m * N + n;
-    float4 v = *reinterpret_cast<const float4*>(w);
-    // four slabs' loads in flight before their adds (the one-at-a-time loop waited for each:
-    // 2.9 TB/s), the adds in the same order as before (bitwise the same sums)
-    int k = 1;
-    for (; k + 3 < s; k += 4) {
-      const float4 u0 = *reinterpret_cast<const float4*>(w + k * slab);
-      const float4 u1 = *reinterpret_cast<const float4*>(w + (k + 1) * slab);
-      const float4 u2 = *reinterpret_cast<const float4*>(w + (k + 2) * slab);
-      const float4 u3 = *reinterpret_cast<const float4*>(w + (k + 3) * slab);
-      v.x += u0.x; v.y += u0.y; v.z += u0.z; v.w += u0.w;
-      v.x += u1.x; v.y += u1.y; v.z += u1.z; v.w += u1.w;
-      v.x += u2.x; v.y += u2.y; v.z += u2.z; v.w += u2.w;
-      v.x += u3.x; v.y += u3.y; v.z += u3.z; v.w += u3.w;
-    }
-    for (; k < s; ++k) {
-      const float4 u = *reinterpret_cast<const float4*>(w + k * slab);
-      v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-    }
-    float4* c = reinterpret_cast<float4*>(C + m * ldc + n);
-    if (accumulate) {
-      const float4 o = *c;
-      v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-    }
-    st16(c, v, nt);
   }
 }
 

@@ -40,9 +40,10 @@ constexpr int G9_NL = G9_TA / 512 / 4;      // 1-KiB pieces per wave per operand
 // EPI 0: plain products; EPI 4: split-K partial tiles into the f32 workspace slab of their
 // k-range (as v7 EPI 4: unit = split * tiles + tile, pl.nk = stages per split, pl.nk_all =
 // stages of the whole product -- whole stages past it are issued with empty descriptors).
-// ER (early release; 0 = the schedule above, the library launches 4 -- DPC_G9_ER /
-// DPC_G9_FWD_ER): phase 0 reads ALL of stage t's k-step-1 fragments
-// in its first ER groups (16 / ER reads per group, one per MFMA gap), then lgkmcnt(0) + an extra
+// ER (early release; 0 = the schedule above.  The planner launches 4 for every product but the
+// split-K slabs of gemm9_kernel<4, false, false, 0, 0>, which keep ER 0; ER 2 is a lab arm of
+// bench/g7lab.hip): phase 0 reads ALL of stage t's k-step-1 fragments in its first ER groups
+// (16 / ER reads per group, one per MFMA gap), then lgkmcnt(0) + an extra
 // barrier -- every wave is done with stage t's buffer -- and the DMA of stage t+2 starts right
 // there (pairs in phase 0 groups ER..7, the rest in phase 1), instead of in phase 1.  A stage's
 // pieces then have ~1.5-1.75 bodies (3,000-3,600 MFMA cycles) to land before the mid wait that
@@ -271,8 +272,7 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
     G9_E0(4, FIRST); G9_E0(5, FIRST); G9_E0(6, FIRST); G9_E0(7, FIRST);                             \
     /* mid: stage t+1 landed (younger: the 2 P0 pieces of stage t+2 issued in phase 0, and in  */ \
     /* a tile's first body the last epilogue's stores between the two)                         */ \
-    if (ABL & 64) {                                                                                 \
-    } else if ((CREDIT) && credit > 0) {                                                            \
+    if ((CREDIT) && credit > 0) {                                                                   \
       if (pl.store_cnt >= 48) g7_wait<63>(); /* (the counter's limit: stage t+1 still done) */       \
       else g7_wait<31 + 2 * P0>();                                                                  \
     } else {                                                                                        \
@@ -292,8 +292,7 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
     G9_G0(0, FIRST); G9_G0(1, FIRST); G9_G0(2, FIRST); G9_G0(3, FIRST);                             \
     G9_G0(4, FIRST); G9_G0(5, FIRST); G9_G0(6, FIRST); G9_G0(7, FIRST);                             \
     /* mid: stage t+1 landed (younger: nothing, or the last epilogue's stores) */                   \
-    if (ABL & 64) {                                                                                 \
-    } else if ((CREDIT) && credit > 0) {                                                            \
+    if ((CREDIT) && credit > 0) {                                                                   \
       if (pl.store_cnt >= 48) g7_wait<63>();                                                        \
       else g7_wait<31>();                                                                           \
     } else {                                                                                        \
@@ -340,7 +339,7 @@ __global__ __launch_bounds__(256, 1) void gemm9_kernel(GemmArgs p, unsigned long
     const int uu = local + u * pl.grid;
     int m0, n0;
     g7_tile(pl, uu % ntiles, m0, n0);
-    if (pl.debug & 1) {
+    if (pl.debug & 1) {  // (bench/g7lab.hip's no_epilogue variants; the planner leaves 0)
     } else if constexpr (EPI == 4) {
       GemmArgs q = p;  // the k-range's slab: [M][N] f32 at ws + split * M * N
       q.C = static_cast<float*>(p.ws) + (long long)(uu / ntiles) * p.M * p.N;

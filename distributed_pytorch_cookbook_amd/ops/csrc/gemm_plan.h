@@ -64,7 +64,7 @@ struct G7Plan {
   int nk_all;  // k-slices of the whole product (slices of a unit past it read zeros)
   int splits;
   int store_cnt;  // vector-memory ops the epilogue issues per wave-lane (0: unknown -> no credit)
-  int debug;      // experiments only (DPC_G7_DEBUG): 1 = no epilogue (main-loop ablations: ABL, bench/g7lab.hip)
+  int debug;      // bench/g7lab.hip only (the planner leaves 0): 1 = no epilogue (main-loop ablations, ABL)
 };
 
 // (common.h's Act values and gemm7_kern.h's slice depth; gemm.hip static_asserts they agree)
@@ -98,7 +98,6 @@ struct GemmSettings {
   // -1 = unset), else DPC_G7_ACTLDS / DPC_G7_RESLDS (default on)
   int act_lds = -1, act_lds_env = 1;
   int res_lds = -1, res_lds_env = 1;
-  int debug = 0;  // DPC_G7_DEBUG -> G7Plan::debug
   // Resident-CU budget.  v7 / v8 / v9 are persistent: their grid is sized to fill every CU (one
   // / two 160 KiB workgroups each), so a kernel already resident on a CU -- an RCCL collective on
   // the comm stream -- would hold back that CU's GEMM workgroup until the collective ends, and
@@ -349,8 +348,7 @@ inline bool plan7(const GemmArgs& a, const GemmSettings& st, const GemmImpl& row
   // read nothing per element and issue every store of a full tile (no column-sum atomics)
   const bool no_loads = !a.residual && !a.act_bwd && !a.accumulate && !a.colsum;
   pl.store_cnt = (no_loads && (s == 1 || slab) && !v8) ? ((a.out_f32 || slab ? 64 : 32) + (a.aux_out ? 32 : 0)) : 0;
-  pl.debug = st.debug;
-  if (st.debug & 13) pl.store_cnt = 0;
+  pl.debug = 0;
   p.grid = (unsigned)pl.grid;
   p.block = 256;
   p.steps[0] = p.steps[1] = p.steps[2] = GS_NONE;

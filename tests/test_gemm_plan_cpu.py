@@ -18,6 +18,8 @@ import subprocess
 
 import pytest
 
+import gemm_cases
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPS = os.path.join(ROOT, "distributed_pytorch_cookbook_amd", "ops")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "gemm_plan_cases.txt")
@@ -155,3 +157,19 @@ def test_every_compiled_kernel_is_reached():
         compiled = {ln.strip() for ln in f if ln.strip() and not ln.startswith("#")}
     named = set(re.findall(r"gemm(?:7|7d|9)_kernel<[^>]*>", "\n".join(w.split("\t")[1] for w in _golden())))
     assert named == compiled, (sorted(compiled - named), sorted(named - compiled))
+
+
+def test_every_compiled_kernel_has_gpu_cases(tool):
+    """The case table of test_gemm_instantiations_gpu.py covers every line of gemm_parts.txt:
+    each identity has a recorded case that a running process can set up, and a grown form of one
+    in which a workgroup streams at least two units while the plan still names that identity."""
+    def explain(cs):
+        r = subprocess.run([tool], input="\n".join(cs) + "\n", capture_output=True, text=True, check=True)
+        return [ln.split("\t")[1] for ln in r.stdout.splitlines()]
+
+    by = gemm_cases.cases_by_identity()
+    idents = gemm_cases.identities()
+    assert not [i for i in idents if i not in by]
+    assert explain([by[i][0] for i in idents]) == [dict(gemm_cases.golden())[by[i][0]] for i in idents]
+    two = {i: gemm_cases.two_unit_case(i, by[i], explain) for i in idents}
+    assert not [i for i in idents if two[i] is None]
