@@ -4,7 +4,17 @@ Semantics follow ``/root/reference/models/gpt.py:68-105``: causal mask (key j > 
 is excluded), optional key-padding mask (``True`` = padded key, excluded), softmax in
 f32, output heads merged back to ``[T, H*hd]``.  One deliberate difference: a query row
 whose every key is masked yields 0 here (the reference's finfo.min / -1e9 arithmetic
-yields an ill-defined average); such rows only occur for all-padding sequences.
+yields an ill-defined average); such rows occur for all-padding sequences and, under the
+causal mask, for the queries inside a run of left padding.  For such a row every path
+(bf16, f32, torch) gives o = +0 and lse = +inf, and the backward gives exact zeros for
+its dq; dk and dv of a padded key are exact zeros too, however far its score lies above
+the row's lse (the kernels select the zero, they do not multiply by it).
+Precision of the f32 path: the forward sums each score q . k in f64 (one f32 rounding
+per pair of products), so o stays within 1e-5 of its largest element of the f64 result
+even when raw scores reach several hundred -- where plain f32 math, and this kernel
+with one f32 accumulator, were 1e-5 to 4e-5 off.  It costs the f32 forward about 2 x
+(tests/test_attention_scores_gpu.py and csrc/attention_f32.hip have the measurements).
+The backward forms P from f32-accumulated scores; its gradients are held to 1e-4.
 
 HIP path (bf16, head_dim 32, 64 or 128 natively): ``dpc_attn_fwd`` / ``dpc_attn_bwd`` flash
 kernels (``csrc/attention.hip``) -- O(S) memory, f32 log-sum-exp saved for the backward.

@@ -17,6 +17,10 @@
 // by rows (32 rows x columns 2s, 2s+1 per instruction) use HD + 2 floats (64 distinct banks);
 // the forward's V, read by columns at rows kappa and kappa + 4, uses HD + 8 (the halves 32
 // banks apart).
+// Forward scores are summed in f64 (fwd_kernel's tile loop): one f32 accumulator over head_dim was
+// 1.2e-5 .. 4.0e-5 of the largest |o| off on scores of several hundred (tests/attn_cases.py), past
+// the 1e-5 this path is held to; with the f64 sums at most 3.8e-6.  Cost, MI355X, N 8, S 1024,
+// causal: hd 64 (H 12) 244 -> 451 us, hd 32 (H 24) 230 -> 407 us, hd 128 (H 6) 249 -> 591 us.
 #include "common.h"
 
 namespace dpc {
@@ -109,13 +113,17 @@ __global__ __launch_bounds__(256, HD >= 128 ? 1 : 2) void fwd_kernel(AttnArgs p)
   float qf[HD / 2];  // Q[q][2 s + h]
 #pragma unroll
   for (int s = 0; s < HD / 2; ++s) qf[s] = q < S ? Q[(tok0 + q) * p.ld_qkv + 2 * s + hh] : 0.f;
-  const float c = p.scale * LOG2E;
   const int kend = p.causal ? min(S, qb * 128 + 128) : S;
   const int ntiles = (kend + T - 1) / T;
-  float m = -INFINITY, l = 0.f;
+  // The running max and the scores are held in f64 (see the tile loop); l and O stay f32.
+  double m = -INFINITY;
+  float l = 0.f;
+  const double cd = (double)p.scale * 1.4426950408889634;
   floatx16 o[NDT];
 #pragma unroll
   for (int d = 0; d < NDT; ++d) zero(o[d]);
+  floatx16 zacc;
+  zero(zacc);
 
   float4 rk[HD / 16], rv[HD / 16];
   ld_tile<HD>(rk, K, p.ld_qkv, 0, S);
@@ -133,12 +141,23 @@ __global__ __launch_bounds__(256, HD >= 128 ? 1 : 2) void fwd_kernel(AttnArgs p)
     if (!(p.causal && kt0 > q0 + 31)) {
       const float* ks = sk[cur];
       const float* vs = sv[cur];
-      floatx16 sc[2];
+      // Scores summed in f64: every k-step's MFMA starts from a zero accumulator (two products,
+      // one f32 rounding) and is added to an f64 sum.  One f32 accumulator over the HD / 2 k-steps
+      // rounds at the magnitude of the running sum every step; with |q . k| of several hundred
+      // (one large coordinate suffices) that is ~1e-5 in the exponent after the scale, and in
+      // every P -- what plain f32 math gives, and 1.2e-5 .. 4.0e-5 of the largest |o| on the
+      // score cases of tests/attn_cases.py.  The exponent s c - m is formed in f64 as well.
+      double sd[2][16];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
-        zero(sc[kb]);
 #pragma unroll
-        for (int s = 0; s < HD / 2; ++s) sc[kb] = mma(ks[(kb * 32 + (lane & 31)) * LK + 2 * s + hh], qf[s], sc[kb]);
+        for (int r = 0; r < 16; ++r) sd[kb][r] = 0.0;
+#pragma unroll
+        for (int s = 0; s < HD / 2; ++s) {
+          const floatx16 part = mma(ks[(kb * 32 + (lane & 31)) * LK + 2 * s + hh], qf[s], zacc);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sd[kb][r] += (double)part[r];
+        }
       }
       const bool need_mask = (p.causal && kt0 + T - 1 > q0) || (kt0 + T > S) || pad;
       if (need_mask) {
@@ -149,18 +168,18 @@ __global__ __launch_bounds__(256, HD >= 128 ? 1 : 2) void fwd_kernel(AttnArgs p)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int kl = kb * 32 + crow(r, lane);
-            if (kl > lim || ((pm >> kl) & 1ull)) sc[kb][r] = -INFINITY;
+            if (kl > lim || ((pm >> kl) & 1ull)) sd[kb][r] = -INFINITY;
           }
       }
-      float mx = -INFINITY;
+      double mx = -INFINITY;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sc[kb][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * c;
-      const float mn = fmaxf(m, mx);
+        for (int r = 0; r < 16; ++r) mx = fmax(mx, sd[kb][r]);
+      mx = fmax(mx, __shfl_xor(mx, 32, 64)) * cd;
+      const double mn = fmax(m, mx);
       if (mn > m) {  // exact online softmax (no lazy threshold on the f32 path)
-        const float alpha = (m == -INFINITY) ? 0.f : exp2f(m - mn);
+        const float alpha = (m == -INFINITY) ? 0.f : exp2f((float)(m - mn));
         l *= alpha;
 #pragma unroll
         for (int d = 0; d < NDT; ++d)
@@ -168,12 +187,13 @@ __global__ __launch_bounds__(256, HD >= 128 ? 1 : 2) void fwd_kernel(AttnArgs p)
           for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
         m = mn;
       }
-      const float nmu = (m == -INFINITY) ? 0.f : -m;
+      const double nmu = (m == -INFINITY) ? 0.0 : -m;
+      floatx16 sc[2];
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float e = exp2f(fmaf(sc[kb][r], c, nmu));
+          const float e = exp2f((float)fma(sd[kb][r], cd, nmu));
           sc[kb][r] = e;
           l += e;
         }
@@ -203,7 +223,7 @@ __global__ __launch_bounds__(256, HD >= 128 ? 1 : 2) void fwd_kernel(AttnArgs p)
     for (int d = 0; d < NDT; ++d)
 #pragma unroll
       for (int r = 0; r < 16; ++r) O[d * 32 + crow(r, lane)] = o[d][r] * inv;
-    if (hh == 0) p.lse[(long long)bh * S + q] = (l > 0.f) ? (m + log2f(l)) / LOG2E : INFINITY;
+    if (hh == 0) p.lse[(long long)bh * S + q] = (l > 0.f) ? (float)((m + (double)log2f(l)) / 1.4426950408889634) : INFINITY;
   }
 }
 

@@ -7,6 +7,7 @@ import math
 import pytest
 import torch
 
+import attn_cases as ac
 import kernel_checks as kc
 from kernel_checks import (MARGIN, MARGIN_ATTN, assert_elem_bound, assert_guards_intact, assert_local_close,
                            attention_plain, gemm_elem_bound, guarded, row_col_err)
@@ -170,6 +171,85 @@ def test_attention_bwd_plain_is_the_gradient(causal, with_pad):
     (gr,) = torch.autograd.grad(o, x, do)
     mine = kc.attention_bwd_plain(qkv, do, o.detach(), lse.detach(), N, S, H, hd, pad, causal, dtype=torch.float64)
     assert torch.allclose(mine, gr, rtol=1e-10, atol=1e-12)
+
+
+def test_attention_bwd_plain_with_dead_rows():
+    """Left padding under the causal mask (query rows with no allowed key) and an all-padding
+    sequence: the explicit backward equals autograd wherever a row lives, and is exactly zero in
+    dq of the dead rows, in dk / dv of the padded keys and in all of the dead sequence."""
+    N, S, H, hd = 3, 37, 2, 16
+    E = H * hd
+    g = torch.Generator().manual_seed(5)
+    qkv = torch.randn(N * S, 3 * E, generator=g, dtype=torch.float64)
+    do = torch.randn(N * S, E, generator=g, dtype=torch.float64)
+    pad = torch.zeros(N, S, dtype=torch.bool)
+    pad[0, :9] = True
+    pad[1, 11:20] = True
+    pad[2, :] = True
+    x = qkv.clone().requires_grad_(True)
+    o, lse = attention_plain(x, N, S, H, hd, pad, True)
+    assert torch.equal(o[:9], torch.zeros(9, E, dtype=torch.float64)) and torch.isinf(lse[:H, :9]).all()
+    assert torch.equal(o[2 * S:], torch.zeros(S, E, dtype=torch.float64)) and torch.isinf(lse[2 * H:]).all()
+    (gr,) = torch.autograd.grad(o, x, do)
+    mine = kc.attention_bwd_plain(qkv, do, o.detach(), lse.detach(), N, S, H, hd, pad, True, dtype=torch.float64)
+    assert torch.isfinite(mine).all()
+    assert torch.allclose(mine[:2 * S], gr[:2 * S], rtol=1e-10, atol=1e-12)
+    zeros = torch.zeros(S, E, dtype=torch.float64)
+    assert torch.equal(mine[:9, :E], zeros[:9])                    # dq of the dead query rows
+    assert torch.equal(mine[:9, E:], torch.cat([zeros[:9]] * 2, 1))  # dk, dv of the padded keys
+    assert torch.equal(mine[S + 11:S + 20, E:], torch.cat([zeros[:9]] * 2, 1))
+    assert torch.equal(mine[2 * S:], torch.cat([zeros] * 3, 1))
+
+
+# ---- the score cases of tests/attn_cases.py reach what they are for (else the GPU tests of
+# test_attention_scores_gpu.py would pass without running the arms they were written for)
+@pytest.mark.parametrize("hd,S", ac.SHAPES)
+@pytest.mark.parametrize("profile,G", ac.PROFILES)
+def test_attention_score_cases_reach_their_arms(profile, G, hd, S):
+    N, H = ac.N_SEQ, ac.HEADS
+    E = H * hd
+    qkv = ac.attention_score_case(profile, G, hd, S)
+    do = ac.attention_score_dout(profile, G, hd, S)
+    assert qkv.dtype == torch.bfloat16 and qkv.shape == (N * S, 3 * E) and do.shape == (N * S, E)
+    assert torch.equal(qkv, ac.attention_score_case(profile, G, hd, S))  # a function of its arguments
+    assert (qkv[:, :E].reshape(-1, H, hd)[:, :, 0] == ac.A_Q).all()
+    for causal in (True, False):
+        for with_pad in (False, True):
+            what = f"{profile} {G} hd {hd} S {S} causal {causal} pad {with_pad}"
+            pad = ac.attention_score_mask(N, S) if with_pad else None
+            ev = ac.rescale_event_rows(qkv, N, S, H, hd, pad, causal)
+            if profile == "falling":
+                assert ev == 0.0, (what, ev)
+            elif G != 70:
+                assert ev >= (0.05 if with_pad else 0.30), (what, ev)
+            if G == 70 and ((profile == "rising" and causal) or (profile == "falling" and with_pad)):
+                ex = ac.masked_excess(qkv, N, S, H, hd, pad, causal)
+                assert ex >= 128.0, (what, ex)
+            o64, lse64, g64, o_ideal, lse32, g_ideal = ac.score_references(qkv, do, N, S, H, hd, pad, causal)
+            fr, _ = row_col_err(o_ideal, o64)
+            assert 1e-3 < fr < 4e-3, (what, fr)
+            assert torch.isfinite(g64).all() and torch.isfinite(g_ideal.float()).all(), what
+            dead = ~torch.isfinite(lse64)  # [N H, S]
+            assert bool(dead.any()) == with_pad
+            if with_pad:
+                assert dead[2 * H:].all() and (dead[:H, :140].all() if causal else not dead[:2 * H].any())
+            if (profile, G) in ac.MODERATE:
+                # what the GPU test requires of the inputs before it holds dk / dv to a row bound
+                fk, _ = row_col_err(g_ideal[:, E:2 * E], g64[:, E:2 * E])
+                fv, _ = row_col_err(g_ideal[:, 2 * E:], g64[:, 2 * E:])
+                assert fk <= 0.1 and fv <= 5e-3, (what, fk, fv)
+
+
+def test_attention_score_helpers_see_a_plain_randn_case_as_plain():
+    """With randn inputs (what every other attention test uses) no row rescales with live
+    accumulators and no masked score comes near an exp2 overflow."""
+    N, S, H, hd = 3, 320, 2, 64
+    qkv = torch.randn(N * S, 3 * H * hd, generator=torch.Generator().manual_seed(3)).bfloat16()
+    pad = ac.attention_score_mask(N, S)
+    for causal in (True, False):
+        assert ac.rescale_event_rows(qkv, N, S, H, hd, None, causal) == 0.0
+        assert ac.masked_excess(qkv, N, S, H, hd, pad, causal) < 16.0
+    assert ac.masked_excess(qkv, N, S, H, hd, None, False) == -math.inf
 
 
 def test_elem_close_uses_the_ideals_largest_error():
