@@ -69,6 +69,11 @@ def build_parser(recipe: str = "single") -> argparse.ArgumentParser:
                    help="also checkpoint (model + optimizer + RNG) every N optimizer steps")
     p.add_argument("--no_save", action="store_true")
     p.add_argument("--no_generate", action="store_true")
+    p.add_argument("--temperature", type=float, default=0.0,
+                   help="sample the end-of-epoch texts at this temperature (0 = greedy argmax)")
+    p.add_argument("--top_k", type=int, default=0, help="sampling: keep the k most likely tokens, ties included (0 = off)")
+    p.add_argument("--top_p", type=float, default=1.0, help="sampling: nucleus mass (1.0 = off)")
+    p.add_argument("--sample_seed", type=int, default=0, help="seed of the sampler's counter-based stream")
     p.add_argument("--bucket_mb", type=float, default=128.0, help="DDP gradient bucket size")
     p.add_argument("--reduce_dtype", type=str, default="fp32", choices=["fp32", "bf16"])
     p.add_argument("--no_overlap", action="store_true", help="all-reduce after backward instead of during")

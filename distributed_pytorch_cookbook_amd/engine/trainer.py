@@ -23,7 +23,7 @@ from torch.utils.data import DataLoader, Sampler
 
 from ..parallel.transport import check_peer_comms
 from ..parallel import comm
-from ..utils.batch import generate, prepare_batch
+from ..utils.batch import generate, generate_batch, prepare_batch
 from ..utils.checkpoint import (latest_checkpoint, load_model_state, load_train_state, rng_state,
                                 save_model_state, save_train_state, set_rng_state)
 from ..utils.metrics import mfu, peak_memory_gib, train_flops_per_token
@@ -297,6 +297,15 @@ class Trainer:
     def sample(self):
         e = self.engine
         if not (e.collective_generate or self.log):
+            return
+        a = self.args
+        if getattr(a, "temperature", 0.0) > 0:
+            if self.log:
+                print(f"Sampling from model (temperature={a.temperature}, top_k={a.top_k}, top_p={a.top_p})")
+            for s in generate_batch(e.lm(), list(PROMPTS), self.tok, self.device, temperature=a.temperature,
+                                    top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed):
+                if self.log:
+                    print(s)
             return
         if self.log:
             print("Argmax sampling from model")

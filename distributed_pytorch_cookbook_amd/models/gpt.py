@@ -283,23 +283,28 @@ class TransformerDecoderLM(nn.Module):
         return fused_lm_forward(self, input_ids, position_ids, mask, targets, want_correct, dropout_seed,
                                 last_only)
 
-    def new_kv_cache(self, batch_size: int, max_len: int):
+    def new_kv_cache(self, batch_size: int, max_len: int, ragged: bool = False):
+        """``ragged``: one cache length per sequence (prompts of different lengths in one batch)."""
         from .fused import KVCache, ensure_store
 
         return KVCache(self, batch_size, max_len, next(self.parameters()).device,
-                       ensure_store(self).compute_dtype)
+                       ensure_store(self).compute_dtype, ragged)
 
-    def decode(self, input_ids, position_ids, cache):
-        """Logits ``[N, 1, V]`` of the last of the new tokens, attending over ``cache`` (extended)."""
+    def decode(self, input_ids, position_ids, cache, lens=None):
+        """Logits ``[N, 1, V]`` of the last of the new tokens, attending over ``cache`` (extended).
+        A ragged cache takes right-padded prompts with their true lengths ``lens`` first (logits of
+        row ``lens[n] - 1``), then one token per sequence at its own position (``position_ids``
+        unused: the positions are the cache lengths)."""
         from .fused import kv_decode_forward
 
-        return kv_decode_forward(self, input_ids, position_ids, cache)
+        return kv_decode_forward(self, input_ids, position_ids, cache, lens)
 
-    def graph_decoder(self, cache):
-        """HIP-graph one-token decode step over ``cache`` (None for a sharded store)."""
+    def graph_decoder(self, cache, sampler=None):
+        """HIP-graph one-token decode step over ``cache`` (None for a sharded store).  For a ragged
+        cache the graph may end in ``sampler`` (``ops/sample.py:Sampler``)."""
         from ..parallel.store import LocalStore
         from ..ops.attention import DECODE_MAX_S, decode_supported
-        from .fused import GraphDecoder, ensure_store
+        from .fused import GraphDecoder, RaggedGraphDecoder, ensure_store
 
         store = ensure_store(self)
         # the graphed step runs the HIP decode kernel, which reads the cache length on the
@@ -310,6 +315,8 @@ class TransformerDecoderLM(nn.Module):
         if (not isinstance(store, LocalStore) or cache.capacity > DECODE_MAX_S
                 or store.compute_dtype != torch.bfloat16 or not decode_supported(attn.head_dim)):
             return None
+        if cache.ragged:
+            return RaggedGraphDecoder(self, cache, sampler)
         return GraphDecoder(self, cache)
 
 

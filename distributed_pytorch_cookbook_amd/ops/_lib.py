@@ -192,6 +192,19 @@ class DecodeAttnArgs(ctypes.Structure):
         ("ldqkv", LL), ("ldo", LL),
         ("N", c_int), ("H", c_int), ("hd", c_int), ("Smax", c_int),
         ("scale", c_float),
+        ("per_seq", c_int),  # 0: len is [1] (one length for the batch); 1: len is [N]
+    ]
+
+
+class SampleArgs(ctypes.Structure):
+    """``sample.hip:SampleArgs``."""
+    _fields_ = [
+        ("logits", P), ("counters", P), ("u", P), ("out_tok", P), ("done", P),
+        ("seq", P), ("step", P), ("len", P),
+        ("ld", LL), ("seq_ld", LL), ("eos", LL),
+        ("N", c_int), ("V", c_int), ("top_k", c_int),
+        ("temperature", c_float), ("top_p", c_float),
+        ("seed_lo", c_uint), ("seed_hi", c_uint),
     ]
 
 
@@ -215,6 +228,7 @@ class GemvArgs(ctypes.Structure):
 _FUNCS = {
     "dpc_decode_attn": DecodeAttnArgs,
     "dpc_gemv": GemvArgs,
+    "dpc_sample": SampleArgs,
     "dpc_embedding_bwd_sorted": EmbBwdArgs,
     "dpc_gemm": GemmArgs,
     "dpc_gemm_f32": GemmArgs,

@@ -236,9 +236,11 @@ def decode_supported(head_dim: int) -> bool:
     return head_dim > 0 and head_dim % 8 == 0 and head_dim <= 256
 
 
-def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None):
+def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=False):
     """One new token per sequence against a KV cache: appends its key / value at
     ``length`` (device int64 [1], cached tokens so far) and returns o [N, H*hd].
+    ``per_seq``: ``length`` is int64 [N], one per sequence (a ragged batch); a sequence whose
+    cache is full (``length[n] >= S_max``) appends nothing and gets a zero output row.
 
     qkv [N, 3*H*hd]; kc, vc [N, S_max, H*hd].  HIP path: ``dpc_decode_attn``
     (``csrc/decode.hip``); reads the length on the device, so it can be graph-captured.
@@ -246,7 +248,16 @@ def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None):
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     N, E = qkv.shape[0], heads * head_dim
     Smax = kc.shape[1]
+    if length.numel() != (N if per_seq else 1):
+        raise ValueError("decode_attention: length must be [N] with per_seq, [1] without")
     if not (qkv.is_cuda and qkv.dtype == torch.bfloat16):
+        if per_seq:
+            o = torch.zeros(N, E, device=qkv.device, dtype=qkv.dtype)
+            for n, pos in enumerate(length.tolist()):
+                if 0 <= pos < Smax:
+                    o[n:n + 1] = decode_attention(qkv[n:n + 1], kc[n:n + 1], vc[n:n + 1], length[n:n + 1],
+                                                  heads, head_dim, scale)
+            return o
         pos = int(length)
         q, k, v = split_qkv(qkv, heads, head_dim)
         kc[:, pos] = k
@@ -264,6 +275,6 @@ def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None):
     o = torch.empty(N, E, device=qkv.device, dtype=torch.bfloat16)
     args = _lib.DecodeAttnArgs(qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), o=o.data_ptr(),
                                len=length.data_ptr(), ldqkv=qkv.stride(0), ldo=E, N=N, H=heads,
-                               hd=head_dim, Smax=Smax, scale=scale)
+                               hd=head_dim, Smax=Smax, scale=scale, per_seq=int(bool(per_seq)))
     _lib.call("dpc_decode_attn", args, qkv.device)
     return o

@@ -1,7 +1,7 @@
 // Single-query attention for KV-cache decoding (one new token per sequence).
 //
 // One workgroup per (sequence, head), 256 threads: append the new key / value row to the
-// cache at the device-side length, scores of the query against every cached key (LDS),
+// cache at the device-side length (one for the batch, or one per sequence), scores of the query against every cached key (LDS),
 // softmax, then P.V with each thread owning 8 head dims of a strided subset of the keys and
 // an LDS reduction over the subsets.  The length is read on the device, so the launch has
 // no length-dependent shape and the decode step can be captured in a HIP graph.  Decode is
@@ -15,10 +15,11 @@ struct DecodeAttnArgs {
   void* kc;                  // [N][Smax][E] bf16 key cache
   void* vc;                  // [N][Smax][E] bf16 value cache
   void* o;                   // [N][ldo] bf16
-  const long long* len;      // device: number of cached tokens before this one
+  const long long* len;      // device: number of cached tokens before this one ([1], or [N] with per_seq)
   long long ldqkv, ldo;
   int N, H, hd, Smax;
   float scale;
+  int per_seq;               // 0: one length for the whole batch; 1: len[n] per sequence
 };
 
 constexpr int DA_NT = 256;
@@ -32,7 +33,11 @@ __global__ __launch_bounds__(DA_NT) void decode_attn_kernel(DecodeAttnArgs p) {
   const int tid = threadIdx.x;
   const int n = blockIdx.x / p.H, h = blockIdx.x % p.H;
   const int hd = p.hd, E = p.H * hd;
-  const long long pos = *p.len;
+  const long long pos = p.per_seq ? p.len[n] : *p.len;
+  if (pos < 0 || pos >= p.Smax) {  // a full cache: append nothing, attend to nothing
+    if (tid < hd) static_cast<bf16_t*>(p.o)[n * p.ldo + h * hd + tid] = 0;
+    return;
+  }
   const int L = (int)pos + 1;
   const bf16_t* qrow = static_cast<const bf16_t*>(p.qkv) + n * p.ldqkv + h * hd;
   const bf16_t* knew = qrow + E;

@@ -12,6 +12,12 @@ on the last position only (``last_only``) where the model supports it, and a mod
 ``decode`` (``TransformerDecoderLM``) runs a KV-cache decode instead while the context fits.  ``model`` is any
 callable ``model(input_ids=..., position_ids=...) -> logits [1, s, V]`` (an LM or a
 parallel engine's forward), so FSDP / pipeline engines run it on every rank.
+
+``generate_batch`` generates for several prompts at once with temperature / top-k / top-p sampling
+(``ops/sample.py``; ``temperature=0`` is greedy): right-padded prompts share one ragged KV cache
+(a length per sequence), and on a GPU the whole step -- embedding, layers, LM head, sampler --
+is one replayed HIP graph that needs nothing from the host; the loop reads the ``done`` flags
+every 8 steps only.  Finished sequences keep stepping and emit EOS; each is cut at its first EOS.
 """
 from __future__ import annotations
 
@@ -39,7 +45,10 @@ def prepare_batch(batch, pad_id: int, device):
 
 
 @torch.inference_mode()
-def generate(model, prompt: str, tokenizer, device, max_new_tokens: int = 20, use_cache: bool = True) -> str:
+def generate(model, prompt: str, tokenizer, device, max_new_tokens: int = 20, use_cache: bool = True,
+             temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> str:
+    if temperature > 0 or top_k > 0 or top_p < 1.0:  # sampling: the batched loop with one prompt
+        return generate_batch(model, [prompt], tokenizer, device, max_new_tokens, temperature, top_k, top_p, seed)[0]
     batch = tokenizer([prompt], truncation=True, max_length=256, return_tensors="pt")
     input_ids = batch["input_ids"].to(device)
     # the learned position table bounds the context: slide a window past it
@@ -91,3 +100,87 @@ def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens):
         else:
             logits = model.decode(tok, torch.full((1, 1), len(out) - 1, device=device, dtype=torch.long), cache)
     return tokenizer.decode(out, skip_special_tokens=True)
+
+
+def _last_only(model) -> bool:
+    try:
+        fwd = model.forward if isinstance(model, torch.nn.Module) else model
+        return "last_only" in inspect.signature(fwd).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+DONE_POLL = 8  # steps between two reads of the done flags
+
+
+@torch.inference_mode()
+def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, temperature: float = 0.0,
+                   top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> list:
+    """Continuations of ``prompts`` (a list of strings), sampled with ``temperature`` / ``top_k`` /
+    ``top_p`` from the counter-based stream of ``seed`` (row n of the batch draws
+    ``sample_uniform(seed, n, step)``: the same arguments give the same text, on every rank)."""
+    from ..ops.sample import Sampler
+
+    device = torch.device(device)
+    ids = [tokenizer([p], truncation=True, max_length=256, return_tensors="pt")["input_ids"][0] for p in prompts]
+    lens = [int(t.numel()) for t in ids]
+    N = len(ids)
+    if N == 0 or max_new_tokens <= 0:
+        return [tokenizer.decode(t.tolist(), skip_special_tokens=True) for t in ids]
+    eos = tokenizer.eos_token_id
+    eos = -1 if eos is None else int(eos)
+    max_pos = getattr(model, "max_position_embeddings", None) or 1 << 30
+    sampler = Sampler(N, max_new_tokens, device, temperature, top_k, top_p, seed, eos)
+    if hasattr(model, "decode") and max(lens) + max_new_tokens <= max_pos:
+        _sample_cached(model, ids, lens, sampler, device, max_new_tokens)
+        new = sampler.sequences()
+    else:
+        new = [_sample_recompute(model, t, n, sampler, device, max_new_tokens, max_pos) for n, t in enumerate(ids)]
+    return [tokenizer.decode(t.tolist() + g, skip_special_tokens=True) for t, g in zip(ids, new)]
+
+
+def _sample_cached(model, ids, lens, sampler, device, max_new_tokens):
+    """One prefill of the right-padded prompts into a ragged KV cache, then one token per sequence
+    per step: a replayed HIP graph ending in the sampler where the model has one, else eagerly."""
+    N, S = len(ids), max(lens)
+    padded = torch.zeros(N, S, dtype=torch.int64)
+    for n, t in enumerate(ids):
+        padded[n, :lens[n]] = t
+    cache = model.new_kv_cache(N, S + max_new_tokens, ragged=True)
+    logits = model.decode(padded.to(device), None, cache, lens=lens)
+    sampler(logits[:, 0])  # (the prefill has set the lengths: token 0 goes to position lens[n])
+    dec = None
+    if device.type == "cuda" and hasattr(model, "graph_decoder"):
+        dec = model.graph_decoder(cache, sampler)  # None if the store is sharded (FSDP) or f32
+    for i in range(1, max_new_tokens):
+        if i % DONE_POLL == 0 and bool(sampler.done.all()):
+            break
+        if dec is not None:
+            dec.step()
+        else:
+            sampler(model.decode(sampler.tok, None, cache)[:, 0])
+
+
+def _sample_recompute(model, ids, row, sampler, device, max_new_tokens, max_pos):
+    """The full-recompute loop of ``generate`` for one prompt (any callable: FSDP / pipeline engine
+    forwards), sampling with the torch twin; ``row`` is the prompt's row of the batch, which its
+    uniforms depend on."""
+    from ..ops.sample import sample_reference, sample_uniform
+
+    last_only = _last_only(model)
+    input_ids = ids.view(1, -1).to(device)
+    out = []
+    for i in range(max_new_tokens):
+        ctx = input_ids[:, -max_pos:]
+        position_ids = torch.arange(ctx.shape[1], device=device).unsqueeze(0)
+        if last_only:
+            logits = model(input_ids=ctx, position_ids=position_ids, last_only=True)
+        else:
+            logits = model(input_ids=ctx, position_ids=position_ids)
+        u = torch.tensor([sample_uniform(sampler.seed, row, i)], dtype=torch.float32, device=logits.device)
+        tok = int(sample_reference(logits[:, -1].float(), sampler.temperature, sampler.top_k, sampler.top_p, u))
+        if tok == sampler.eos:
+            break
+        out.append(tok)
+        input_ids = torch.cat([input_ids, torch.tensor([[tok]], dtype=input_ids.dtype, device=device)], 1)
+    return out

@@ -1,0 +1,282 @@
+"""The sampler kernel (``csrc/sample.hip``), the per-sequence decode attention and the graphed,
+sync-free generation loop on the GPU."""
+import math
+
+import pytest
+import torch
+
+from kernel_checks import MARGIN_ATTN, assert_guards_intact, assert_local_close, guarded
+
+from distributed_pytorch_cookbook_amd.models.fused import vocab_ld
+from distributed_pytorch_cookbook_amd.models.gpt import TransformerDecoderLM
+from distributed_pytorch_cookbook_amd.ops import _lib
+from distributed_pytorch_cookbook_amd.ops.attention import decode_attention
+from distributed_pytorch_cookbook_amd.ops.sample import sample_logits, sample_uniform
+from distributed_pytorch_cookbook_amd.utils.batch import generate_batch
+from distributed_pytorch_cookbook_amd.utils.tokenizer import ByteTokenizer
+
+pytestmark = pytest.mark.gpu
+dev = "cuda"
+BF, F32 = torch.bfloat16, torch.float32
+
+ROWS = 64
+CONFIGS = [(3.0, 50257), (1.0, 50257), (6.0, 1000)]
+TEMPERATURE, TOP_K, TOP_P = 0.8, 50, 0.9
+_rows_cache = {}
+
+
+def config_rows(i):
+    """The 64 rows of configuration i, drawn row after row from one CPU stream over the three
+    configurations in order (made once, never modified)."""
+    if not _rows_cache:
+        torch.manual_seed(0)
+        for c, (scale, V) in enumerate(CONFIGS):
+            _rows_cache[c] = torch.stack([(torch.randn(V) * scale).bfloat16() for _ in range(ROWS)])
+    return _rows_cache[i]
+
+
+def strided(rows):
+    """The rows in a ``vocab_ld``-strided device buffer whose padding columns hold +1e4 (a sampler
+    that reads them as candidates draws them at once)."""
+    N, V = rows.shape
+    buf = torch.full((N, vocab_ld(V)), 1e4, dtype=BF, device=dev)
+    buf[:, :V] = rows.to(dev)
+    return buf[:, :V]
+
+
+def draw(logits, counters=None, **kw):
+    N = logits.shape[0]
+    counters = torch.zeros(N, dtype=torch.int64, device=dev) if counters is None else counters
+    out = torch.full((N, 1), -7, dtype=torch.int64, device=dev)
+    sample_logits(logits, counters=counters, out_tok=out, **kw)
+    return out[:, 0].cpu()
+
+
+def oracle_row(row, temperature, top_k, top_p):
+    """The definition in f64 for one row: (kept, w, ambiguous) -- the kept mask, exp(z - max), and
+    the top-k survivors whose strictly-greater mass lies within 1e-4 of top_p."""
+    z = row.double() / temperature
+    vals, inv, counts = torch.unique(z, return_inverse=True, return_counts=True)  # ascending
+    count_gt = counts.sum() - torch.cumsum(counts, 0)
+    keep_k = count_gt[inv] < top_k if top_k > 0 else torch.ones_like(z, dtype=torch.bool)
+    w = torch.exp(z - z.max())
+    mass = torch.zeros_like(vals).index_add_(0, inv, w * keep_k)
+    q_gt = ((mass.sum() - torch.cumsum(mass, 0)) / mass.sum())[inv]
+    kept = keep_k & ((q_gt < top_p) | (z == z.max()))
+    ambiguous = keep_k & ((q_gt - top_p).abs() <= 1e-4)
+    return kept, w, ambiguous
+
+
+@pytest.mark.parametrize("ci", range(len(CONFIGS)))
+def test_sampler_exact_draw_against_f64(ci):
+    rows = config_rows(ci)
+    V = rows.shape[1]
+    u = torch.tensor([sample_uniform(1234, r, 7) for r in range(ROWS)], dtype=F32)
+    tok = draw(strided(rows), temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, u=u.to(dev)).tolist()
+    assert all(0 <= t < V for t in tok), "a padding column was drawn"
+    # the same rows packed tight (an odd row stride at V = 50257: rows off the 16-B boundary)
+    assert draw(rows.to(dev), temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, u=u.to(dev)).tolist() == tok
+    n_ambiguous, largest = 0, 0
+    for r in range(ROWS):
+        kept, w, amb = oracle_row(rows[r], TEMPERATURE, TOP_K, TOP_P)
+        largest = max(largest, int(kept.sum()))
+        t = tok[r]
+        if amb.any():
+            n_ambiguous += 1
+            assert kept[t] or amb[t], (r, t)
+            continue
+        assert kept[t], (r, t)
+        cum = torch.cumsum(w * kept, 0)
+        Z = cum[-1].item()
+        lo, hi = (cum[t] - w[t]).item() - 1e-5 * Z, cum[t].item() + 1e-5 * Z
+        assert lo <= u[r].double().item() * Z <= hi, (r, t, lo / Z, u[r].item(), hi / Z)
+    print(f"config {CONFIGS[ci]}: {n_ambiguous} ambiguous rows, kept sets up to {largest}")
+    assert n_ambiguous <= 4
+
+
+@pytest.mark.parametrize("V", [7, 1000, 50257])
+def test_sampler_greedy_lowest_index_on_ties(V):
+    torch.manual_seed(V)
+    x = (torch.randn(5, V) * 2).bfloat16()
+    top = x.max() + 1
+    x[0, V - 1] = top
+    x[1, 0] = x[1, V - 1] = top
+    x[2, V // 2] = x[2, V // 2 + 1] = x[2, V - 2] = top
+    x[3, 3] = x[3, 5] = top
+    want = torch.tensor([V - 1, 0, V // 2, 3, int((x[4] == x[4].max()).nonzero()[0])])
+    assert torch.equal(draw(strided(x), temperature=0.0), want)
+    # top_k = 1 at u = 0: the first of the ties again
+    assert torch.equal(draw(strided(x), temperature=0.8, top_k=1, u=torch.zeros(5, device=dev)), want)
+
+
+def test_sampler_distribution_chi2():
+    """8192 hash draws from one V = 8 vector at top_k = 5: Pearson's chi-squared against the f64
+    probabilities below 33.4, the 1 - 1e-6 quantile at 4 degrees of freedom."""
+    vec = torch.tensor([2.0, 1.0, 0.5, 0.0, -0.5, -1.0, -3.0, 1.5]).bfloat16()
+    kept = [0, 1, 2, 3, 7]
+    p = torch.zeros(8, dtype=torch.float64)
+    p[kept] = torch.softmax(vec.double()[kept], 0)
+    n = 8192
+    tok = draw(vec.repeat(n, 1).to(dev), temperature=1.0, top_k=5, seed=3)
+    counts = torch.bincount(tok, minlength=8).double()
+    assert counts[[4, 5, 6]].sum() == 0 and counts.sum() == n
+    chi2 = (((counts - n * p) ** 2)[kept] / (n * p[kept])).sum().item()
+    print(f"chi2 = {chi2:.2f}")
+    assert chi2 < 33.4
+
+
+def test_sampler_counters_and_reproducibility():
+    logits = strided(config_rows(2))
+    kw = dict(temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, seed=9)
+    counters = torch.zeros(ROWS, dtype=torch.int64, device=dev)
+    a = draw(logits, counters, **kw)
+    b = draw(logits, counters, **kw)
+    assert counters.tolist() == [2] * ROWS
+    assert not torch.equal(a, b)
+    counters.zero_()
+    assert torch.equal(draw(logits, counters, **kw), a) and torch.equal(draw(logits, counters, **kw), b)
+    # the hash is the host twin's: an explicit u from it draws the same tokens
+    u = torch.tensor([sample_uniform(9, r, 1) for r in range(ROWS)], dtype=F32, device=dev)
+    assert torch.equal(draw(logits, u=u, **{k: v for k, v in kw.items() if k != "seed"}), b)
+
+
+def test_sampler_done_flags_and_sequence_buffer():
+    logits = strided(config_rows(2))
+    kw = dict(temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, seed=9)
+    free = draw(logits, **kw)
+    eos = int(free[5])  # the token row 5 draws: it (and every row that draws the same) must set its flag
+    done = torch.zeros(ROWS, dtype=torch.bool, device=dev)
+    done[[0, 7]] = True
+    seq = guarded((ROWS, 3), torch.int64, dev, fill=-1)
+    step = torch.tensor([1] * (ROWS - 1) + [3], dtype=torch.int64, device=dev)  # the last row: past the buffer
+    lens = torch.arange(ROWS, dtype=torch.int64, device=dev)
+    tok = draw(logits, done=done, eos=eos, seq=seq, step=step, lens=lens, **kw)
+    want = free.clone()
+    want[[0, 7]] = eos
+    assert torch.equal(tok, want)
+    assert torch.equal(done.cpu(), want == eos) and done[5]
+    assert torch.equal(seq[:-1, 1].cpu(), want[:-1]) and (seq[:, [0, 2]] == -1).all() and seq[-1, 1] == -1
+    assert_guards_intact(seq)
+    assert step.tolist() == [2] * (ROWS - 1) + [4] and torch.equal(lens.cpu(), torch.arange(ROWS) + 1)
+
+
+# ---------------------------------------------------------------- ragged decode attention
+def _decode_ref(qkv, k0, v0, n, L, H, hd, dt):
+    E = H * hd
+    q = qkv[n, :E].to(dt).reshape(H, 1, hd)
+    k = k0[n, :L].to(dt).reshape(L, H, hd).transpose(0, 1)
+    v = v0[n, :L].to(dt).reshape(L, H, hd).transpose(0, 1)
+    return (torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(hd), -1) @ v).reshape(H, hd)
+
+
+@pytest.mark.parametrize("hd", [40, 64, 256])
+def test_decode_attention_ragged_edges(hd):
+    """Lengths 0, 17 and 299 in one launch over guarded caches: row ``len[n]`` of sequence n
+    receives the new key / value and nothing else changes."""
+    torch.manual_seed(7)
+    N, H, Smax = 3, 3, 300
+    E = H * hd
+    lens = [0, 17, 299]
+    k0 = torch.randn(N, Smax, E, device=dev).bfloat16()
+    v0 = torch.randn(N, Smax, E, device=dev).bfloat16()
+    kc, vc = guarded((N, Smax, E), BF, dev, fill=k0), guarded((N, Smax, E), BF, dev, fill=v0)
+    qkv = torch.randn(N, 3 * E, device=dev).bfloat16()
+    length = torch.tensor(lens, device=dev, dtype=torch.int64)
+    o = decode_attention(qkv, kc, vc, length, H, hd, per_seq=True)
+    for n, pos in enumerate(lens):
+        k0[n, pos], v0[n, pos] = qkv[n, E:2 * E], qkv[n, 2 * E:]
+    assert torch.equal(kc, k0) and torch.equal(vc, v0)
+    assert_guards_intact(kc, vc)
+    for n, pos in enumerate(lens):
+        ref, ideal = (_decode_ref(qkv, k0, v0, n, pos + 1, H, hd, dt) for dt in (torch.float64, F32))
+        assert_local_close(o[n].reshape(H, hd), ref, ideal.bfloat16(), MARGIN_ATTN, axes="rows",
+                           what=f"ragged decode o, sequence {n}")
+
+    # one shared length == the same length per sequence, bit for bit
+    outs = []
+    for per_seq in (False, True):
+        ka, va = k0.clone(), v0.clone()
+        ln = torch.full((N if per_seq else 1,), 37, device=dev, dtype=torch.int64)
+        outs.append((decode_attention(qkv, ka, va, ln, H, hd, per_seq=per_seq), ka, va))
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
+
+    # a full cache: nothing is appended and that row's output is zero
+    kc2, vc2 = guarded((N, Smax, E), BF, dev, fill=k0), guarded((N, Smax, E), BF, dev, fill=v0)
+    full = torch.tensor([5, Smax, Smax + 3], device=dev, dtype=torch.int64)
+    o2 = decode_attention(qkv, kc2, vc2, full, H, hd, per_seq=True)
+    k1, v1 = k0.clone(), v0.clone()
+    k1[0, 5], v1[0, 5] = qkv[0, E:2 * E], qkv[0, 2 * E:]
+    assert torch.equal(kc2, k1) and torch.equal(vc2, v1)
+    assert_guards_intact(kc2, vc2)
+    assert torch.count_nonzero(o2[1:]) == 0 and torch.count_nonzero(o2[0]) > 0
+
+
+# ---------------------------------------------------------------- end to end
+def _model():
+    torch.manual_seed(0)
+    with torch.device(dev):
+        m = TransformerDecoderLM(256, 64, 4, 2, 50257, 128, activation="gelu")
+    m.eval()
+    return m
+
+
+def test_ragged_prefill_and_graphed_steps_match_single_sequences():
+    """Three right-padded prompts of lengths 5, 20 and 33 share a ragged cache; the logits after
+    the prefill and after each of 6 teacher-forced graphed steps are those of each sequence alone."""
+    m = _model()
+    lens, steps = [5, 20, 33], 6
+    g = torch.Generator().manual_seed(1)
+    full = [torch.randint(0, 50257, (l + steps,), generator=g).to(dev) for l in lens]
+    padded = torch.zeros(3, max(lens), dtype=torch.int64, device=dev)
+    for n, l in enumerate(lens):
+        padded[n, :l] = full[n][:l]
+
+    def check(lg, t):
+        for n, l in enumerate(lens):
+            ids = full[n][None, :l + t]
+            ref = m(ids, torch.arange(l + t, device=dev)[None])[:, -1:]
+            err = ((lg[n:n + 1].float() - ref.float()).norm() / ref.float().norm()).item()
+            assert err < 2e-2, (n, t, err)
+
+    with torch.no_grad():
+        cache = m.new_kv_cache(3, max(lens) + steps, ragged=True)
+        check(m.decode(padded, None, cache, lens=lens), 0)
+        dec = m.graph_decoder(cache)
+        assert dec is not None
+        for t in range(steps):
+            tok = torch.stack([full[n][l + t] for n, l in enumerate(lens)]).view(3, 1)
+            check(dec.step(tok), t + 1)
+        assert cache.lens == [l + steps for l in lens] and cache.len_t.tolist() == cache.lens
+    assert _lib.is_loaded()
+
+
+class Ids(ByteTokenizer):
+    """Decodes to the token ids themselves, so that the texts compared below hide no token."""
+
+    def decode(self, ids, skip_special_tokens=False):
+        return " ".join(str(int(i)) for i in ids)
+
+
+def _new_tokens(text, prompt):
+    ids = [int(t) for t in text.split()]
+    n = len(prompt.encode())
+    assert ids[:n] == ByteTokenizer().encode(prompt)
+    return ids[n:]
+
+
+def test_generate_batch_seeded_text_and_eos_cut():
+    m, tok = _model(), Ids()
+    prompts = ["The big brown cat ", "One day, ", "She said that nobody would ever "]
+    kw = dict(max_new_tokens=12, temperature=0.8, top_k=40, top_p=0.95, seed=1)
+    a = generate_batch(m, prompts, tok, torch.device(dev), **kw)
+    assert a == generate_batch(m, prompts, tok, torch.device(dev), **kw)
+    new = [_new_tokens(t, p) for t, p in zip(a, prompts)]
+    assert all(len(x) == 12 and all(0 <= t < 50257 for t in x) for x in new)
+    assert a != generate_batch(m, prompts, tok, torch.device(dev), **dict(kw, seed=2))
+    # the 4th token of sequence 1 as EOS: that sequence is cut there, the others are unchanged
+    # (up to their own first occurrence of it)
+    tok.eos_token_id = new[1][3]
+    cut = [x[:x.index(tok.eos_token_id)] if tok.eos_token_id in x else x for x in new]
+    assert len(cut[1]) <= 3
+    b = generate_batch(m, prompts, tok, torch.device(dev), **kw)
+    assert [_new_tokens(t, p) for t, p in zip(b, prompts)] == cut
