@@ -21,14 +21,13 @@ Q, K, V weights are adjacent in the flat layout, so ``[Wq; Wk; Wv]`` is a view.
 """
 from __future__ import annotations
 
-import math
 import os
 from dataclasses import dataclass
 from typing import Optional
 
 import torch
 
-from ..ops.attention import DECODE_MAX_S, attention_bwd, attention_fwd, decode_attention
+from ..ops.attention import attention_bwd, attention_fwd
 from ..ops.elementwise import bias_act_bwd
 from ..ops.dropout import dropout_residual
 from ..ops.embedding import embedding_bwd, embedding_fwd
@@ -634,243 +633,3 @@ def fused_lm_forward(model, input_ids, position_ids, mask=None, targets=None, wa
         return head_logits(model, x, store, getattr(x, "_dpc_tail", None)).reshape(N, S, -1)
     loss, n_valid, n_correct = run_head(model, store, x, targets, training, want_correct)
     return LMOutput(loss, n_valid, n_correct if want_correct else None)
-
-
-class KVCache:
-    """Keys / values of every layer for the tokens decoded so far: ``[N, S_max, H*hd]`` each
-    in the compute dtype (GPT-2 XL at S_max = 1024: 2 x 48 x 1024 x 1600 x 2 B = 315 MB per
-    sequence).  ``ragged``: one length per sequence -- ``len_t`` is ``[N]`` with the host copy
-    ``lens``, so right-padded prompts of different lengths share the batch."""
-
-    def __init__(self, model, N, S_max, device, dtype, ragged=False):
-        self.k, self.v = [], []
-        for layer in model.decoder.layers:
-            E = layer.attn.heads * layer.attn.head_dim
-            # zeroed: the graphed step reads the whole capacity (masked, but 0 * NaN = NaN)
-            self.k.append(torch.zeros(N, S_max, E, device=device, dtype=dtype))
-            self.v.append(torch.zeros(N, S_max, E, device=device, dtype=dtype))
-        self.len = 0
-        self.capacity = S_max
-        self.ragged = bool(ragged)
-        self.len_t = torch.zeros(N if ragged else 1, device=device, dtype=torch.int64)  # device copy for the graph
-        self.lens = [0] * N if ragged else None
-
-
-def _cached_attention(qkv, cache, li, N, n, H, hd):
-    """Append the n new tokens' K/V to layer li's cache and attend to every cached key.
-
-    Prefill (empty cache) is the flash-attention kernel over the n tokens; a decode step is
-    n queries against ``start + n`` keys -- a memory-bound read of the cache (GEMV-shaped,
-    no tiles to fill), done as two batched products in f32."""
-    E = H * hd
-    start = cache.len
-    L = start + n
-    q3 = qkv.view(N, n, 3, E)
-    cache.k[li][:, start:L] = q3[:, :, 1]
-    cache.v[li][:, start:L] = q3[:, :, 2]
-    if start == 0:
-        return attention_fwd(qkv, N, n, H, hd, None, causal=True)
-    q = q3[:, :, 0].float().reshape(N, n, H, hd).transpose(1, 2)             # [N, H, n, hd]
-    k = cache.k[li][:, :L].float().reshape(N, L, H, hd).transpose(1, 2)     # [N, H, L, hd]
-    v = cache.v[li][:, :L].float().reshape(N, L, H, hd).transpose(1, 2)
-    sc = (q @ k.transpose(-1, -2)) * (1.0 / math.sqrt(hd))                  # [N, H, n, L]
-    if n > 1:  # causal inside the new block: query i sees keys < start + i + 1
-        qi = torch.arange(n, device=qkv.device)[:, None] + start
-        sc = sc.masked_fill(torch.arange(L, device=qkv.device)[None, :] > qi, float("-inf"))
-    o = torch.softmax(sc, -1) @ v                                            # [N, H, n, hd]
-    return o.transpose(1, 2).reshape(N * n, E).to(qkv.dtype), None
-
-
-def kv_decode_forward(model, input_ids, position_ids, cache, lens=None):
-    """Incremental forward for greedy decoding: runs only the new tokens (the whole prompt
-    on the first call, then one token per call) through the layers, extends ``cache`` and
-    returns the logits of the last new token, ``[N, 1, V]``.  Same kernels as the training
-    forward (LayerNorm, QKV / FFN GEMMs with fused epilogues, the LM head); the reference
-    recomputes the whole sequence for every token (``/root/reference/utils.py:57-65``)."""
-    if cache.ragged:
-        if cache.len == 0:
-            return ragged_prefill(model, input_ids, lens, cache)
-        if input_ids.shape[1] != 1 or cache.len + 1 > cache.capacity:
-            raise ValueError(f"ragged KV cache: one token per step, {cache.len} + 1 <= {cache.capacity}")
-        return ragged_step(model, ensure_store(model), cache, input_ids, eager=True)
-    store = ensure_store(model)
-    N, n = input_ids.shape
-    if cache.len + n > cache.capacity:
-        raise ValueError(f"KV cache full ({cache.len} + {n} > {cache.capacity})")
-    act = act_code(model.activation)
-    x = run_embeddings(model, store, input_ids, position_ids, False)
-    for li, layer in enumerate(model.decoder.layers):
-        H, hd = layer.attn.heads, layer.attn.head_dim
-        u = layer._unit_id
-        store.pre_forward(u)
-        x, _ = _layer_forward(x, None, layer, store, N, n, act, False, (None, None),
-                              attend=lambda qkv, li=li, H=H, hd=hd: _cached_attention(qkv, cache, li, N, n, H, hd))
-        store.post_forward(u, False)
-    cache.len += n
-    cache.len_t.fill_(cache.len)
-    return head_logits(model, last_rows(x, N, n), store).reshape(N, 1, -1)
-
-
-def _static_attention(qkv, cache, li, N, H, hd):
-    """One query per sequence against the cache, the new key / value appended at the
-    device-side length by the decode kernel: no shape depends on the length, so the step
-    can be graphed."""
-    return decode_attention(qkv, cache.k[li], cache.v[li], cache.len_t, H, hd), None
-
-
-class GraphDecoder:
-    """The one-token decode step (embedding, every layer, LM head, cache append) captured
-    once as a HIP graph and replayed per token: a GPT-2 decode step is a few hundred small
-    launches, so eager decoding is launch-bound (measured in ``bench/generate.py``).  Needs
-    a non-sharded parameter store (single GPU / DDP); FSDP decodes eagerly."""
-
-    def __init__(self, model, cache):
-        self.model, self.cache = model, cache
-        self.store = ensure_store(model)
-        N = cache.k[0].shape[0]
-        self.tok = torch.zeros(N, 1, device=cache.len_t.device, dtype=torch.int64)
-        self.graph = None
-        self.out = None
-
-    def _step(self):
-        model, store, cache = self.model, self.store, self.cache
-        N = self.tok.shape[0]
-        act = act_code(model.activation)
-        x = run_embeddings(model, store, self.tok, cache.len_t.expand(N, 1), False)
-        for li, layer in enumerate(model.decoder.layers):
-            H, hd = layer.attn.heads, layer.attn.head_dim
-            x, _ = _layer_forward(x, None, layer, store, N, 1, act, False, (None, None),
-                                  attend=lambda qkv, li=li, H=H, hd=hd: _static_attention(qkv, cache, li, N, H, hd))
-        cache.len_t.add_(1)
-        return head_logits(model, x, store).reshape(N, 1, -1)
-
-    def step(self, tok):
-        """Append ``tok`` [N, 1] at the cache's current length; logits [N, 1, V] (a view of the
-        graph's output buffer, overwritten by the next step)."""
-        cache = self.cache
-        if cache.len + 1 > cache.capacity:
-            raise ValueError(f"KV cache full ({cache.len} + 1 > {cache.capacity})")
-        self.tok.copy_(tok)
-        if self.graph is None:
-            self._step()                 # eager warm-up (lazy library init), then undo it
-            cache.len_t.sub_(1)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.out = self._step()
-            self.graph = g
-        self.graph.replay()
-        cache.len += 1
-        return self.out
-
-
-# ---------------------------------------------------------------- ragged batches (one length per sequence)
-def ragged_prefill(model, input_ids, lens, cache):
-    """Prefill of right-padded prompts ``input_ids`` [N, S] with true lengths ``lens``: the causal
-    flash-attention forward over all S positions (no pad mask -- a valid row never sees a later
-    key), K / V of every position into the cache, logits [N, 1, V] of row ``lens[n] - 1`` of each
-    sequence.  The padded positions land in the cache beyond ``lens[n]``; the decode kernel reads
-    only ``j < len[n]`` and overwrites them one by one."""
-    store = ensure_store(model)
-    N, S = input_ids.shape
-    lens = [int(l) for l in lens]
-    if len(lens) != N or min(lens) < 1 or max(lens) > S:
-        raise ValueError("ragged prefill: one length in 1..S per sequence")
-    if S > cache.capacity:
-        raise ValueError(f"KV cache full ({S} > {cache.capacity})")
-    act = act_code(model.activation)
-    dev = input_ids.device
-    x = run_embeddings(model, store, input_ids, torch.arange(S, device=dev).expand(N, S), False)
-
-    def attend(qkv, li, H, hd):
-        q3 = qkv.view(N, S, 3, H * hd)
-        cache.k[li][:, :S] = q3[:, :, 1]
-        cache.v[li][:, :S] = q3[:, :, 2]
-        return attention_fwd(qkv, N, S, H, hd, None, causal=True)
-
-    for li, layer in enumerate(model.decoder.layers):
-        H, hd = layer.attn.heads, layer.attn.head_dim
-        u = layer._unit_id
-        store.pre_forward(u)
-        x, _ = _layer_forward(x, None, layer, store, N, S, act, False, (None, None),
-                              attend=lambda qkv, li=li, H=H, hd=hd: attend(qkv, li, H, hd))
-        store.post_forward(u, False)
-    cache.lens = lens
-    cache.len = max(lens)
-    lt = torch.tensor(lens, dtype=torch.int64)
-    cache.len_t.copy_(lt)
-    rows = x.view(N, S, -1)[torch.arange(N, device=dev), (lt - 1).to(dev)].contiguous()
-    return head_logits(model, rows, store).reshape(N, 1, -1)
-
-
-def ragged_step(model, store, cache, tok, sampler=None, eager=False):
-    """One token per sequence of a ragged cache, every length on the device: embedding at positions
-    ``len_t``, the layers with the per-sequence decode attention (appends at ``len_t[n]``), the LM
-    head and -- with ``sampler`` -- the sampler, which writes the next token into ``sampler.tok``
-    and advances the lengths.  No shape depends on a length, so the step can be graphed.  ``eager``:
-    report the unit boundaries to the store (a sharded store gathers its weights there).
-    Returns logits [N, 1, V]."""
-    N = tok.shape[0]
-    act = act_code(model.activation)
-    x = run_embeddings(model, store, tok, cache.len_t.view(N, 1), False)
-    for li, layer in enumerate(model.decoder.layers):
-        H, hd = layer.attn.heads, layer.attn.head_dim
-        if eager:
-            store.pre_forward(layer._unit_id)
-        x, _ = _layer_forward(
-            x, None, layer, store, N, 1, act, False, (None, None),
-            attend=lambda qkv, li=li, H=H, hd=hd: (
-                decode_attention(qkv, cache.k[li], cache.v[li], cache.len_t, H, hd, per_seq=True), None))
-        if eager:
-            store.post_forward(layer._unit_id, False)
-    logits = head_logits(model, x, store)
-    if sampler is not None:
-        sampler(logits, lens=cache.len_t)
-    else:
-        cache.len_t.add_(1)
-    if eager:
-        cache.lens = [l + 1 for l in cache.lens]
-        cache.len += 1
-    return logits.reshape(N, 1, -1)
-
-
-class RaggedGraphDecoder:
-    """``GraphDecoder`` for a ragged cache: one captured graph holds the embedding (positions from
-    ``len_t``), the layers with the per-sequence decode attention, the LM head and, with
-    ``sampler`` (``ops/sample.py:Sampler``), the sampler -- which writes the next token straight
-    into the graph's own ``tok`` buffer and into its column of the output buffer, and advances the
-    lengths.  A replay then needs nothing from the host: ``step()`` with no argument."""
-
-    def __init__(self, model, cache, sampler=None):
-        self.model, self.cache, self.sampler = model, cache, sampler
-        self.store = ensure_store(model)
-        N = cache.k[0].shape[0]
-        self.tok = sampler.tok if sampler is not None else torch.zeros(N, 1, device=cache.len_t.device,
-                                                                       dtype=torch.int64)
-        self.graph = None
-        self.out = None
-
-    def step(self, tok=None):
-        """Append one token per sequence (``tok`` [N, 1]; None: the sampler's last draw, already
-        in place); logits [N, 1, V], a view of the graph's output buffer."""
-        cache = self.cache
-        if cache.len + 1 > cache.capacity:
-            raise ValueError(f"KV cache full ({cache.len} + 1 > {cache.capacity})")
-        if tok is not None:
-            self.tok.copy_(tok)
-        if self.graph is None:
-            # eager warm-up (lazy library init), then undo what it advanced; the cache rows it
-            # appended are rewritten with the same values by the first replay
-            s = self.sampler
-            state = [cache.len_t] + ([s.tok, s.counters, s.done, s.seq, s.step] if s is not None else [])
-            saved = [t.clone() for t in state]
-            ragged_step(self.model, self.store, cache, self.tok, s)
-            for t, v in zip(state, saved):
-                t.copy_(v)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.out = ragged_step(self.model, self.store, cache, self.tok, s)
-            self.graph = g
-        self.graph.replay()
-        cache.lens = [l + 1 for l in cache.lens]
-        cache.len += 1
-        return self.out

@@ -285,7 +285,8 @@ class TransformerDecoderLM(nn.Module):
 
     def new_kv_cache(self, batch_size: int, max_len: int, ragged: bool = False):
         """``ragged``: one cache length per sequence (prompts of different lengths in one batch)."""
-        from .fused import KVCache, ensure_store
+        from .decode import KVCache
+        from .fused import ensure_store
 
         return KVCache(self, batch_size, max_len, next(self.parameters()).device,
                        ensure_store(self).compute_dtype, ragged)
@@ -295,7 +296,7 @@ class TransformerDecoderLM(nn.Module):
         A ragged cache takes right-padded prompts with their true lengths ``lens`` first (logits of
         row ``lens[n] - 1``), then one token per sequence at its own position (``position_ids``
         unused: the positions are the cache lengths)."""
-        from .fused import kv_decode_forward
+        from .decode import kv_decode_forward
 
         return kv_decode_forward(self, input_ids, position_ids, cache, lens)
 
@@ -304,7 +305,8 @@ class TransformerDecoderLM(nn.Module):
         cache the graph may end in ``sampler`` (``ops/sample.py:Sampler``)."""
         from ..parallel.store import LocalStore
         from ..ops.attention import DECODE_MAX_S, decode_supported
-        from .fused import GraphDecoder, RaggedGraphDecoder, ensure_store
+        from .decode import GraphDecoder
+        from .fused import ensure_store
 
         store = ensure_store(self)
         # the graphed step runs the HIP decode kernel, which reads the cache length on the
@@ -315,9 +317,7 @@ class TransformerDecoderLM(nn.Module):
         if (not isinstance(store, LocalStore) or cache.capacity > DECODE_MAX_S
                 or store.compute_dtype != torch.bfloat16 or not decode_supported(attn.head_dim)):
             return None
-        if cache.ragged:
-            return RaggedGraphDecoder(self, cache, sampler)
-        return GraphDecoder(self, cache)
+        return GraphDecoder(self, cache, sampler)
 
 
 PRESETS = {

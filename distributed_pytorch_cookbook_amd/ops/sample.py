@@ -160,6 +160,10 @@ class Sampler:
                              seed=self.seed, counters=self.counters, out_tok=self.tok, done=self.done, eos=self.eos,
                              seq=self.seq, step=self.step, lens=lens)
 
+    def state(self) -> list:
+        """The tensors a call advances (a graph capture saves and restores them around its warm-up)."""
+        return [self.tok, self.counters, self.done, self.seq, self.step]
+
     def sequences(self) -> list:
         """The generated tokens of each sequence, cut at its first ``eos``."""
         out = []

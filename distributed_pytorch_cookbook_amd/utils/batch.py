@@ -7,17 +7,19 @@ on the host before the copy, so no device sync; an all-False padding mask is a n
 and the position ids are built on the device instead of being copied.
 
 ``generate`` is the reference's greedy argmax loop (``utils.py:42-91``): full
-recompute per token, stop at EOS, decode with ``skip_special_tokens``; the LM head runs
-on the last position only (``last_only``) where the model supports it, and a model with
-``decode`` (``TransformerDecoderLM``) runs a KV-cache decode instead while the context fits.  ``model`` is any
-callable ``model(input_ids=..., position_ids=...) -> logits [1, s, V]`` (an LM or a
-parallel engine's forward), so FSDP / pipeline engines run it on every rank.
+recompute per token (``_recompute``), stop at EOS, decode with ``skip_special_tokens``; the LM
+head runs on the last position only (``last_only``) where the model supports it, and a model with
+``decode`` (``TransformerDecoderLM``, ``models/decode.py``) runs a KV-cache decode instead while
+the context fits.  ``model`` is any callable ``model(input_ids=..., position_ids=...) -> logits
+[1, s, V]`` (an LM or a parallel engine's forward), so FSDP / pipeline engines run it on every rank.
 
 ``generate_batch`` generates for several prompts at once with temperature / top-k / top-p sampling
 (``ops/sample.py``; ``temperature=0`` is greedy): right-padded prompts share one ragged KV cache
 (a length per sequence), and on a GPU the whole step -- embedding, layers, LM head, sampler --
-is one replayed HIP graph that needs nothing from the host; the loop reads the ``done`` flags
-every 8 steps only.  Finished sequences keep stepping and emit EOS; each is cut at its first EOS.
+is one replayed HIP graph (``models/decode.py:GraphDecoder``) that needs nothing from the host;
+the loop reads the ``done`` flags every 8 steps only.  Finished sequences keep stepping and emit
+EOS; each is cut at its first EOS.  Without ``decode`` it is the same ``_recompute`` loop, prompt
+by prompt, sampling with the torch twin.
 """
 from __future__ import annotations
 
@@ -53,28 +55,11 @@ def generate(model, prompt: str, tokenizer, device, max_new_tokens: int = 20, us
     input_ids = batch["input_ids"].to(device)
     # the learned position table bounds the context: slide a window past it
     max_pos = getattr(model, "max_position_embeddings", None) or 1 << 30
-    # only the last position's logits are used: skip the [T, V] head GEMM where the model can
-    # (the reference computes every position's logits, utils.py:57-65)
-    try:
-        fwd = model.forward if isinstance(model, torch.nn.Module) else model
-        last_only = "last_only" in inspect.signature(fwd).parameters
-    except (TypeError, ValueError):
-        last_only = False
     if use_cache and hasattr(model, "decode") and input_ids.shape[1] + max_new_tokens <= max_pos:
         return _generate_cached(model, input_ids, tokenizer, device, max_new_tokens)
-    for _ in range(max_new_tokens):
-        ctx = input_ids[:, -max_pos:]
-        s = ctx.shape[1]
-        position_ids = torch.arange(s, device=device).unsqueeze(0)
-        if last_only:
-            logits = model(input_ids=ctx, position_ids=position_ids, last_only=True)
-        else:
-            logits = model(input_ids=ctx, position_ids=position_ids)
-        new_token = int(logits[0, -1].argmax(dim=-1))
-        if new_token == tokenizer.eos_token_id:
-            break
-        input_ids = torch.cat([input_ids, torch.tensor([[new_token]], dtype=input_ids.dtype, device=device)], 1)
-    return tokenizer.decode(input_ids[0].tolist(), skip_special_tokens=True)
+    new = _recompute(model, input_ids, device, max_new_tokens, max_pos, tokenizer.eos_token_id,
+                     lambda logits, i: int(logits.argmax(dim=-1)))
+    return tokenizer.decode(input_ids[0].tolist() + new, skip_special_tokens=True)
 
 
 def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens):
@@ -103,11 +88,32 @@ def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens):
 
 
 def _last_only(model) -> bool:
+    """Whether the model's forward can run the LM head on the last position only."""
     try:
         fwd = model.forward if isinstance(model, torch.nn.Module) else model
         return "last_only" in inspect.signature(fwd).parameters
     except (TypeError, ValueError):
         return False
+
+
+def _recompute(model, input_ids, device, max_new_tokens, max_pos, eos, pick) -> list:
+    """The reference's loop for one prompt ``input_ids`` [1, s]: the whole context again for every
+    token, through any callable (an LM, an FSDP / pipeline engine's forward).  ``pick(logits, i)``
+    chooses token i from the last position's logits [V]; returns the new tokens, stopping before
+    ``eos``."""
+    # only the last position's logits are used: skip the [T, V] head GEMM where the model can
+    # (the reference computes every position's logits, utils.py:57-65)
+    head = {"last_only": True} if _last_only(model) else {}
+    out = []
+    for i in range(max_new_tokens):
+        ctx = input_ids[:, -max_pos:]
+        position_ids = torch.arange(ctx.shape[1], device=device).unsqueeze(0)
+        tok = pick(model(input_ids=ctx, position_ids=position_ids, **head)[0, -1], i)
+        if tok == eos:
+            break
+        out.append(tok)
+        input_ids = torch.cat([input_ids, torch.tensor([[tok]], dtype=input_ids.dtype, device=device)], 1)
+    return out
 
 
 DONE_POLL = 8  # steps between two reads of the done flags
@@ -135,7 +141,8 @@ def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, 
         _sample_cached(model, ids, lens, sampler, device, max_new_tokens)
         new = sampler.sequences()
     else:
-        new = [_sample_recompute(model, t, n, sampler, device, max_new_tokens, max_pos) for n, t in enumerate(ids)]
+        new = [_recompute(model, t.view(1, -1).to(device), device, max_new_tokens, max_pos, eos,
+                          _sampled_pick(sampler, n)) for n, t in enumerate(ids)]
     return [tokenizer.decode(t.tolist() + g, skip_special_tokens=True) for t, g in zip(ids, new)]
 
 
@@ -161,26 +168,13 @@ def _sample_cached(model, ids, lens, sampler, device, max_new_tokens):
             sampler(model.decode(sampler.tok, None, cache)[:, 0])
 
 
-def _sample_recompute(model, ids, row, sampler, device, max_new_tokens, max_pos):
-    """The full-recompute loop of ``generate`` for one prompt (any callable: FSDP / pipeline engine
-    forwards), sampling with the torch twin; ``row`` is the prompt's row of the batch, which its
-    uniforms depend on."""
+def _sampled_pick(sampler, row):
+    """The token rule of ``_recompute`` that samples with the torch twin; ``row`` is the prompt's row
+    of the batch, which its uniforms depend on."""
     from ..ops.sample import sample_reference, sample_uniform
 
-    last_only = _last_only(model)
-    input_ids = ids.view(1, -1).to(device)
-    out = []
-    for i in range(max_new_tokens):
-        ctx = input_ids[:, -max_pos:]
-        position_ids = torch.arange(ctx.shape[1], device=device).unsqueeze(0)
-        if last_only:
-            logits = model(input_ids=ctx, position_ids=position_ids, last_only=True)
-        else:
-            logits = model(input_ids=ctx, position_ids=position_ids)
+    def pick(logits, i):
         u = torch.tensor([sample_uniform(sampler.seed, row, i)], dtype=torch.float32, device=logits.device)
-        tok = int(sample_reference(logits[:, -1].float(), sampler.temperature, sampler.top_k, sampler.top_p, u))
-        if tok == sampler.eos:
-            break
-        out.append(tok)
-        input_ids = torch.cat([input_ids, torch.tensor([[tok]], dtype=input_ids.dtype, device=device)], 1)
-    return out
+        return int(sample_reference(logits[None].float(), sampler.temperature, sampler.top_k, sampler.top_p, u))
+
+    return pick

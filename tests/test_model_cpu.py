@@ -313,6 +313,71 @@ def test_kv_cache_decode_matches_recompute(act):
     assert generate(m, "One day, ", tok, cpu, 8) == generate(m, "One day, ", tok, cpu, 8, use_cache=False)
 
 
+def _decode_model():
+    torch.manual_seed(1)
+    m = TransformerDecoderLM(64, 32, 2, 2, 512, 64, activation="gelu")
+    m.eval()
+    return m
+
+
+def test_ragged_kv_cache_decode_matches_single_sequences():
+    """Eager ragged decode: right-padded prompts of lengths 5, 12 and 9 share one cache; the logits
+    after the prefill and after each of three teacher-forced steps are those of each sequence
+    alone, and the host lengths follow the device ones."""
+    m = _decode_model()
+    lens, steps = [5, 12, 9], 3
+    g = torch.Generator().manual_seed(2)
+    full = [torch.randint(0, 512, (l + steps,), generator=g) for l in lens]
+    padded = torch.zeros(3, max(lens), dtype=torch.int64)
+    for n, l in enumerate(lens):
+        padded[n, :l] = full[n][:l]
+
+    def check(lg, t):
+        for n, l in enumerate(lens):
+            ref = m(full[n][None, :l + t], torch.arange(l + t)[None])[:, -1:]
+            assert torch.allclose(lg[n:n + 1], ref, atol=1e-4, rtol=1e-4), (n, t)
+
+    with torch.no_grad():
+        cache = m.new_kv_cache(3, max(lens) + steps, ragged=True)
+        check(m.decode(padded, None, cache, lens=lens), 0)
+        for t in range(steps):
+            tok = torch.stack([full[n][l + t] for n, l in enumerate(lens)]).view(3, 1)
+            check(m.decode(tok, None, cache), t + 1)
+    assert cache.lens == [8, 15, 12] == cache.len_t.tolist()
+    assert cache.len == 15
+
+
+def _refused(m, cache, ids, pos=None, **kw):
+    """``m.decode`` raises ValueError and leaves the cache's bookkeeping as it was."""
+    before = (cache.len, None if cache.lens is None else list(cache.lens), cache.len_t.tolist())
+    with pytest.raises(ValueError):
+        m.decode(ids, pos, cache, **kw)
+    assert (cache.len, cache.lens, cache.len_t.tolist()) == before
+
+
+def test_kv_cache_refusals_leave_the_cache_untouched():
+    m = _decode_model()
+    ids = torch.randint(0, 512, (2, 16), generator=torch.Generator().manual_seed(3))
+    with torch.no_grad():
+        cache = m.new_kv_cache(2, 8)
+        _refused(m, cache, ids, torch.arange(16).expand(2, -1))  # a block larger than the empty cache
+        m.decode(ids[:, :8], torch.arange(8).expand(2, -1), cache)
+        assert cache.len == 8 and cache.len_t.tolist() == [8]
+        _refused(m, cache, ids[:, 8:9], torch.full((2, 1), 8))  # one token into the full cache
+
+        cache = m.new_kv_cache(2, 9, ragged=True)
+        _refused(m, cache, ids[:, :8], lens=[0, 8])   # an empty prompt
+        _refused(m, cache, ids[:, :8], lens=[3, 9])   # a length beyond the padded width
+        _refused(m, cache, ids[:, :8], lens=[3])      # one length for two sequences
+        _refused(m, cache, ids, lens=[3, 16])         # 16 columns into 9 rows
+        m.decode(ids[:, :8], None, cache, lens=[3, 8])
+        assert (cache.len, cache.lens, cache.len_t.tolist()) == (8, [3, 8], [3, 8])
+        _refused(m, cache, ids[:, 8:10])              # two tokens in one step
+        m.decode(ids[:, 8:9], None, cache)
+        assert (cache.len, cache.lens, cache.len_t.tolist()) == (9, [4, 9], [4, 9])
+        _refused(m, cache, ids[:, 9:10])              # 9 + 1 > 9
+
+
 # ---------------------------------------------------------------- parity with the reference module
 _GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 

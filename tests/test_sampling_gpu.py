@@ -247,7 +247,46 @@ def test_ragged_prefill_and_graphed_steps_match_single_sequences():
             tok = torch.stack([full[n][l + t] for n, l in enumerate(lens)]).view(3, 1)
             check(dec.step(tok), t + 1)
         assert cache.lens == [l + steps for l in lens] and cache.len_t.tolist() == cache.lens
+        # the longest sequence has filled the cache: a further step is refused and changes nothing
+        with pytest.raises(ValueError):
+            dec.step(tok)
+        assert cache.lens == [l + steps for l in lens] and cache.len_t.tolist() == cache.lens
     assert _lib.is_loaded()
+
+
+def test_graphed_sampler_steps_read_their_own_draws():
+    """A graph that ends in the sampler: the warm-up before the capture leaves no draw behind, and
+    the logits of every replay are those of the prompt followed by the tokens the sampler wrote."""
+    from distributed_pytorch_cookbook_amd.ops.sample import Sampler
+
+    m = _model()
+    lens, steps = [5, 20, 33], 4
+    g = torch.Generator().manual_seed(1)
+    prompts = [torch.randint(0, 50257, (l,), generator=g).to(dev) for l in lens]
+    padded = torch.zeros(3, max(lens), dtype=torch.int64, device=dev)
+    for n, l in enumerate(lens):
+        padded[n, :l] = prompts[n]
+    sampler = Sampler(3, 8, dev, temperature=0.8, top_k=40, top_p=0.95, seed=1, eos=-1)
+    with torch.no_grad():
+        cache = m.new_kv_cache(3, max(lens) + 8, ragged=True)
+        logits = m.decode(padded, None, cache, lens=lens)
+        sampler(logits[:, 0])
+        first = sampler.tok[:, 0].clone()
+        dec = m.graph_decoder(cache, sampler)
+        assert dec is not None
+        outs = []
+        for _ in range(steps):
+            dec.step()
+            outs.append(dec.out.clone())
+        assert sampler.counters.tolist() == sampler.step.tolist() == [steps + 1] * 3
+        assert torch.equal(sampler.seq[:, 0], first)
+        assert cache.len_t.tolist() == cache.lens == [l + steps for l in lens]
+        for t, out in enumerate(outs):
+            for n, l in enumerate(lens):
+                ids = torch.cat([prompts[n], sampler.seq[n, :t + 1]])[None]
+                ref = m(ids, torch.arange(l + t + 1, device=dev)[None])[:, -1:]
+                err = ((out[n:n + 1].float() - ref.float()).norm() / ref.float().norm()).item()
+                assert err < 2e-2, (n, t, err)
 
 
 class Ids(ByteTokenizer):
