@@ -9,6 +9,9 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from ..parallel import transport
+from ..utils.profiling import mark
+
 
 class Engine:
     name = "base"
@@ -22,8 +25,21 @@ class Engine:
     scaler = None             # ops.amp.GradScaler when --grad_scaler (reference GradScaler)
 
     clipper = None            # ops.clip.GradClipper when --max_grad_norm > 0
+    graph = False             # the whole step as one HIP graph (GraphedStep)
 
-    def _make_clipper(self, max_grad_norm: float) -> None:
+    # The end of a step is shared (_finish_and_step); an engine describes its own as data:
+    parts = ()                # [(optimizer, its gradients on the device, replicated?)]; the first
+    #                           optimizer's buffer is the one store.finish_grads reports ranges of
+    may_overlap = False       # AdamW range by range while later collectives are still in flight
+    reduce_flag = False       # the ranks hold different gradients: the skip flag is reduced ...
+    flag_group = None         # ... over this group (None: the world)
+    norm_tp = None            # transport whose ranks hold the other pieces of the squared norm
+
+    def _make_scaler_clipper(self, grad_scaler: bool, max_grad_norm: float) -> None:
+        if grad_scaler:
+            from ..ops.amp import GradScaler
+
+            self.scaler = GradScaler(self.device)
         if max_grad_norm and max_grad_norm > 0.0:
             from ..ops.clip import GradClipper
 
@@ -48,16 +64,67 @@ class Engine:
     def train_step(self, batch: dict, targets: torch.Tensor) -> torch.Tensor:
         """One optimizer step; returns the (local) mean loss as a 0-dim device tensor,
         or None on ranks that do not see the loss (non-last pipeline stages)."""
+        out = self._stepper(self._step_body, batch, targets) if self.graph else self._step_body(batch, targets)
+        transport.check_drained(f"the end of a {self.name} step")  # --stream_check (SURVEY.md §5.2)
+        return out
+
+    def _step_body(self, batch, targets):
+        """zero_grad, forward, backward, then ``_finish_and_step``; returns the loss."""
         raise NotImplementedError
+
+    def _finish_and_step(self) -> None:
+        """The end of every engine's step: complete the gradient collectives and step the
+        optimizers (1/dp, the loss scaler's 1/scale and the clip coefficient are folded into
+        AdamW).  Without scaler and clipper an engine that ``may_overlap`` updates each range
+        of the first optimizer's buffer as ``store.finish_grads`` reports it final -- DDP and
+        PP x DP bucket by bucket, FSDP unit by unit -- while the later collectives are still on
+        the comm stream.  Otherwise every gradient comes first (``_step_all``)."""
+        if self.scaler is not None or self.clipper is not None or not self.may_overlap:
+            with mark("comm:finish_grads"):
+                self.store.finish_grads()
+            with mark("optim"):
+                self._step_all()
+            return
+        gs = 1.0 / self.dp_world
+        (opt, _, _), *rest = self.parts
+        with mark("optim"):
+            opt.begin_step()
+            self.store.finish_grads(lambda lo, hi: opt.update(lo, hi, grad_scale=gs))
+            for o, _, _ in rest:
+                o.step(grad_scale=gs)
+
+    def _step_all(self) -> None:
+        """Step the optimizers once every gradient is final: the non-finite check and the
+        global norm must see all of them before any parameter moves."""
+        gs = 1.0 / self.dp_world
+        sc, cl = self.scaler, self.clipper
+        if cl is not None:
+            cl.begin()
+            for _, grad, replicated in self.parts:
+                cl.add(grad, replicated=replicated)
+            cl.reduce(self.norm_tp)
+        if sc is not None:
+            for o, _, _ in self.parts:
+                sc.check(o.grad)
+            if self.reduce_flag:
+                sc.reduce_flag(self.flag_group)
+        if cl is not None:
+            cl.finish(gs, None if sc is None else sc.inv_scale_t)
+        for o, _, _ in self.parts:
+            o.step(grad_scale=gs, **{**(sc.opt_kwargs(o) if sc is not None else {}),
+                                     **(cl.opt_kwargs(o) if cl is not None else {})})
+        if sc is not None:
+            sc.update()
 
     @torch.no_grad()
     def eval_step(self, batch: dict, targets: torch.Tensor):
         """Returns (loss_sum, n_valid, n_correct) device tensors (or None off the last stage)."""
-        raise NotImplementedError
+        out = self.model(**batch, targets=targets, want_correct=True)
+        return out.loss * out.n_valid, out.n_valid, out.n_correct
 
     def lm(self):
         """Callable(input_ids=, position_ids=) -> logits for ``generate``."""
-        raise NotImplementedError
+        return self.model
 
     def full_state_dict(self):
         """Canonical model state on the logging rank (collective for sharded engines)."""
@@ -81,8 +148,6 @@ class Engine:
         gathered units, in-flight sends -- after a failed HIP-graph capture: nothing the
         capture recorded ever ran, so the eager retry must issue everything again (a bucket
         left marked as launched would never be all-reduced: silent rank divergence)."""
-        from ..parallel import transport
-
         for obj in (getattr(self, "store", None), getattr(self, "p2p", None)):
             if obj is not None and hasattr(obj, "reset_step_state"):
                 obj.reset_step_state()

@@ -17,7 +17,6 @@ from ..ops.optim import FlatAdamW
 from ..parallel import comm
 from ..parallel.ddp import DDPStore
 from ..parallel.store import LocalStore
-from ..parallel.transport import check_drained
 from ..utils.profiling import mark
 from .base import Engine, GraphedStep
 
@@ -43,14 +42,14 @@ class DataParallelEngine(Engine):
         else:
             self.store = LocalStore(model, device, compute_dtype=compute_dtype)
         self.opt = FlatAdamW(self.store.master, self.store.grads, lr=lr, shadow=self.store.shadow)
-        if grad_scaler:
-            from ..ops.amp import GradScaler
-
-            self.scaler = GradScaler(self.device)
-        self._make_clipper(max_grad_norm)
+        self._make_scaler_clipper(grad_scaler, max_grad_norm)
+        # all-reduced gradients are identical on every rank, so are the skip flag and the norm
+        # (its sum has a fixed order: ops/clip.py) -- no collective for either
+        self.parts = [(self.opt, self.store.grads, True)]
+        tp = getattr(self.store, "tp", None)
+        self.may_overlap = tp is not None and tp.active and self.store.master.is_cuda
         # HIP-graph "compile": at one rank, or across ranks when the gradient all-reduces ride
         # the capturable native RCCL transport
-        tp = getattr(self.store, "tp", None)
         self.graph = graph and self.device.type == "cuda" and (self.dp_world == 1 or (tp is not None and tp.capturable()))
         self._stepper = GraphedStep(self, [self.opt])
 
@@ -61,60 +60,8 @@ class DataParallelEngine(Engine):
             out = self.model(**batch, targets=targets)
         with mark("bwd"):  # (the DDP bucket all-reduces are enqueued from inside it: "comm:*")
             self._scaled(out.loss).backward()
-        with mark("optim"):
-            return self._optim(out)
-
-    def _optim(self, out):
-        if self.scaler is not None or self.clipper is not None:
-            # the non-finite check and the global norm need every bucket reduced before any
-            # parameter moves; all-reduced gradients are identical on every rank, so are the flag
-            # and the norm (its sum has a fixed order: ops/clip.py) -- no collective for either
-            if isinstance(self.store, DDPStore):
-                self.store.finish_grads()
-            kw = {}
-            if self.scaler is not None:
-                self.scaler.check(self.store.grads)
-                kw = self.scaler.opt_kwargs(self.opt)
-            if self.clipper is not None:
-                cl = self.clipper
-                cl.begin()
-                cl.add(self.store.grads, replicated=True)
-                kw.update(cl.finish(1.0 / self.dp_world, kw.get("grad_scale_t")))
-            self.opt.step(grad_scale=1.0 / self.dp_world, **kw)
-            if self.scaler is not None:
-                self.scaler.update()
-            return out.loss.detach()
-        if isinstance(self.store, DDPStore) and self.store.tp.active and self.store.master.is_cuda:
-            # bucket by bucket: AdamW of the buckets already reduced runs on the compute stream
-            # while the last ones (the embeddings, whose backward comes last) are still being
-            # all-reduced on the comm stream
-            st = self.store
-            st.launch_all()
-            self.opt.begin_step()
-            for bi in range(len(st.buckets)):
-                with mark("comm:wait_bucket"):
-                    st.wait_bucket(bi)
-                lo, hi = st.bucket_range(bi)
-                self.opt.update(lo, hi, grad_scale=1.0 / self.dp_world)
-            st.reset_buckets()
-            return out.loss.detach()
-        if isinstance(self.store, DDPStore):
-            self.store.finish_grads()
-        self.opt.step(grad_scale=1.0 / self.dp_world)
+        self._finish_and_step()
         return out.loss.detach()
-
-    def train_step(self, batch, targets):
-        out = self._stepper(self._step_body, batch, targets) if self.graph else self._step_body(batch, targets)
-        check_drained(f"the end of a {self.name} step")  # --stream_check
-        return out
-
-    @torch.no_grad()
-    def eval_step(self, batch, targets):
-        out = self.model(**batch, targets=targets, want_correct=True)
-        return out.loss * out.n_valid, out.n_valid, out.n_correct
-
-    def lm(self):
-        return self.model
 
     # ------------------------------------------------------------------ state
     def full_state_dict(self):

@@ -15,7 +15,6 @@ import torch
 from ..ops.optim import FlatAdamW
 from ..parallel import comm
 from ..parallel.fsdp import FSDPStore
-from ..parallel.transport import check_drained
 from ..utils.profiling import mark
 from .base import Engine, GraphedStep
 
@@ -45,21 +44,25 @@ class FSDPEngine(Engine):
         grad = st.grads_host if st.cpu_offload else st.grads
         self.opt = FlatAdamW(st.master, grad, lr=lr, shadow=st.shadow)
         self.opt_rep = FlatAdamW(st.rep_master, st.rep_grads, lr=lr)  # replicated 1-D params
-        if grad_scaler:
-            from ..ops.amp import GradScaler
-
-            self.scaler = GradScaler(self.device)
-        self._make_clipper(max_grad_norm)
+        self._make_scaler_clipper(grad_scaler, max_grad_norm)
+        # The shards differ per rank: the skip flag and the shards' squared norm are reduced over
+        # the group; the replicated 1-D gradients are all-reduced by finish_grads and counted
+        # once.  The norm is taken on the device gradients (--cpu_offload: before they are
+        # consumed on the host), over the whole of st.grads: its padding (units are padded to
+        # W x 64 elements) and the slots of the 1-D parameters inside the units are zero --
+        # zero_grad clears the buffer, the unit gradient buffers start as zeros, the kernels
+        # write parameter views only and the 1-D gradients live in rep_grads -- so nothing is
+        # excluded (tests/test_grad_clip_cpu.py checks the norm against the unsharded engine's)
+        self.parts = [(self.opt, st.grads, False), (self.opt_rep, st.rep_grads, True)]
+        self.reduce_flag, self.flag_group, self.norm_tp = True, group, st.tp
+        # unit by unit: AdamW of the units already reduce-scattered on the compute stream while
+        # the remaining reduce-scatters are still on the comm stream
+        self.may_overlap = st.sharded and st.tp.active and not st.cpu_offload
         # HIP-graph "compile" of the whole sharded step (gathers, reduce-scatters, AdamW);
         # not with --cpu_offload, whose optimizer runs on the host
         self.graph = (graph and self.device.type == "cuda" and not st.cpu_offload
                       and (not st.sharded or st.tp.capturable()))
         self._stepper = GraphedStep(self, [self.opt, self.opt_rep])
-
-    def train_step(self, batch, targets):
-        out = self._stepper(self._step_body, batch, targets) if self.graph else self._step_body(batch, targets)
-        check_drained(f"the end of a {self.name} step")  # --stream_check
-        return out
 
     def _step_body(self, batch, targets):
         st = self.store
@@ -68,67 +71,26 @@ class FSDPEngine(Engine):
             out = self.model(**batch, targets=targets)
         with mark("bwd"):  # (re-gathers and reduce-scatters enqueued inside)
             self._scaled(out.loss).backward()
-        if self.scaler is None and self.clipper is None and not st.cpu_offload and st.sharded and st.tp.active:
-            # unit by unit: AdamW of the units already reduce-scattered on the compute stream
-            # while the remaining reduce-scatters are still on the comm stream (not with the
-            # scaler or clipping: both need every gradient before any parameter moves)
-            with mark("optim"):
-                st.finish_grads_and_update(self.opt, self.opt_rep, grad_scale=1.0 / self.dp_world)
-            return out.loss.detach()
+        if st.cpu_offload:
+            self._finish_and_step_on_host()
+        else:
+            self._finish_and_step()
+        return out.loss.detach()
+
+    def _finish_and_step_on_host(self):
+        """--cpu_offload: the sharded optimizer lives on the host."""
+        st = self.store
         with mark("comm:finish_grads"):
             st.finish_grads()
         with mark("optim"):
-            return self._optim(out)
-
-    def _optim(self, out):
-        st = self.store
-        cl = self.clipper
-        if st.cpu_offload and self.scaler is None and cl is None and not _OFFLOAD_SYNC:
-            # pipelined host AdamW: overlaps the next step's forward (FSDPStore.host_step)
-            st.host_step(self.opt, grad_scale=1.0 / self.dp_world)
-            self.opt_rep.step(grad_scale=1.0 / self.dp_world)
-            return out.loss.detach()
-        if cl is not None:
-            # on the device gradients, before any D2H copy of --cpu_offload.  The shards differ
-            # per rank (summed over the group); the replicated 1-D gradients were all-reduced by
-            # finish_grads and are counted once.  The whole of st.grads is summed: its padding
-            # (units are padded to W x 64 elements) and the slots of the 1-D parameters inside the
-            # units are zero here -- zero_grad clears the buffer, the unit gradient buffers start
-            # as zeros, the kernels write parameter views only and the 1-D gradients live in
-            # rep_grads -- found zero, so nothing is excluded (tests/test_grad_clip_cpu.py checks
-            # the norm against the unsharded engine's)
-            cl.begin()
-            cl.add(st.grads, replicated=False)
-            cl.add(st.rep_grads, replicated=True)
-            if st.sharded:
-                cl.reduce(st.tp)
-        if st.cpu_offload:
+            if self.scaler is None and self.clipper is None and not _OFFLOAD_SYNC:
+                # pipelined host AdamW: overlaps the next step's forward (FSDPStore.host_step)
+                st.host_step(self.opt, grad_scale=1.0 / self.dp_world)
+                self.opt_rep.step(grad_scale=1.0 / self.dp_world)
+                return
             st.grads_host.copy_(st.grads, non_blocking=True)
             torch.cuda.current_stream().synchronize()  # grads_host D2H landed
-        kw, kw_rep = {}, {}
-        if self.scaler is not None:
-            # shards differ per rank: the skip decision is reduced over the group
-            sc = self.scaler
-            sc.check(self.opt.grad)
-            sc.check(self.opt_rep.grad)
-            sc.reduce_flag(self.dp_group)
-            kw, kw_rep = sc.opt_kwargs(self.opt), sc.opt_kwargs(self.opt_rep)
-        if cl is not None:
-            cl.finish(1.0 / self.dp_world, None if self.scaler is None else self.scaler.inv_scale_t)
-            kw, kw_rep = {**kw, **cl.opt_kwargs(self.opt)}, {**kw_rep, **cl.opt_kwargs(self.opt_rep)}
-        self.opt.step(grad_scale=1.0 / self.dp_world, **kw)
-        self.opt_rep.step(grad_scale=1.0 / self.dp_world, **kw_rep)
-        if self.scaler is not None:
-            self.scaler.update()
-        return out.loss.detach()
-
-    @torch.no_grad()
-    def eval_step(self, batch, targets):
-        out = self.model(**batch, targets=targets, want_correct=True)
-        return out.loss * out.n_valid, out.n_valid, out.n_correct
-
-    def lm(self):
-        return self.model
+            self._step_all()  # (the clipper reads the device gradients: ``parts``)
 
     def full_state_dict(self):
         return self.store.gather_full(self.store.master, dst_rank=0)

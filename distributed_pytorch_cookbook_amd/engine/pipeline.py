@@ -32,7 +32,6 @@ from ..parallel.pipeline import (P2P, partition, run_schedule, schedule_1f1b, sc
                                  stage_costs, unit_costs)
 from ..parallel.store import LocalStore
 from ..parallel.transport import TorchTransport, make_mesh_transports
-from ..parallel.transport import check_drained
 from ..utils.profiling import mark
 from .base import Engine, GraphedStep
 
@@ -48,11 +47,7 @@ class PipelineEngine(Engine):
                  reduce_dtype=torch.float32, max_grad_norm: float = 0.0):
         self.device = torch.device(device)
         self.model = model
-        self._make_clipper(max_grad_norm)
-        if grad_scaler:
-            from ..ops.amp import GradScaler
-
-            self.scaler = GradScaler(self.device)
+        self._make_scaler_clipper(grad_scaler, max_grad_norm)
         world = comm.world_size()
         if pp * dp != world:
             raise ValueError(f"pp ({pp}) x dp ({dp}) must equal the world size ({world})")
@@ -111,6 +106,16 @@ class PipelineEngine(Engine):
             self.store = LocalStore(model, device, compute_dtype=compute_dtype, units=self.my_units)
         self.store.accum_steps = self.n_micro
         self.opt = FlatAdamW(self.store.master, self.store.grads, lr=lr, shadow=self.store.shadow)
+        # Every stage holds different gradients: one skip decision for the whole job.  The stages
+        # hold disjoint units (no weight is tied across stages), so the global norm sums the
+        # stages' squares over the pipeline group; with PP x DP the replica all-reduce has already
+        # made a stage's gradients identical across its replicas.
+        self.parts = [(self.opt, self.store.grads, False)]
+        self.reduce_flag, self.flag_group, self.norm_tp = True, None, self.pp_tp
+        # bucket by bucket, as the DDP engine does: AdamW of the buckets whose replica all-reduce
+        # has landed runs while the later ones are still on the links (a stage's buckets launch
+        # from its last micro-batch's backward -- or W -- passes, unit by unit)
+        self.may_overlap = self.dp_tp.active and (dp > 1 or force_dist)  # (the store rides dp_tp)
         self.p2p = P2P(self.pp_tp, self.stage, pp, self.device, wire_dtype=wire_dtype)
         self.pp_ranks = pp_ranks
         self.D = model.dim
@@ -134,8 +139,7 @@ class PipelineEngine(Engine):
             return self.n_micro_req
         if self.pp == 1:
             return 1
-        mfac = getattr(self, "_mfac", 4)
-        return max(d for d in range(1, min(N, mfac * self.pp) + 1) if N % d == 0)
+        return max(d for d in range(1, min(N, self._mfac * self.pp) + 1) if N % d == 0)
 
     def _split(self, batch, targets):
         N = batch["input_ids"].shape[0]
@@ -171,11 +175,6 @@ class PipelineEngine(Engine):
         return (mb * S, self.D)
 
     # ------------------------------------------------------------------ training
-    def train_step(self, batch, targets):
-        out = self._stepper(self._step_body, batch, targets) if self.graph else self._step_body(batch, targets)
-        check_drained(f"the end of a {self.name} step")  # --stream_check
-        return out
-
     def _step_body(self, batch, targets):
         st = self.store
         st.zero_grad()
@@ -227,25 +226,8 @@ class PipelineEngine(Engine):
             order = (schedule_gpipe if self.schedule == "gpipe" else schedule_1f1b)(self.n_micro, self.stage, self.pp)
         run_schedule(order, self.first, self.last, forward, backward, self.p2p, shape, wgrad=wgrad)
         assert not wq, "zero-bubble schedule left weight gradients unrun"
-        if isinstance(st, DDPStore) and st.tp.active and self.scaler is None and self.clipper is None:
-            # bucket by bucket, as the DDP engine does: AdamW of the buckets whose replica
-            # all-reduce has landed runs while the later ones are still on the links (a stage's
-            # buckets launch from its last micro-batch's backward -- or W -- passes, unit by unit)
-            with mark("optim"):
-                st.launch_all()
-                self.opt.begin_step()
-                for bi in range(len(st.buckets)):
-                    with mark("comm:wait_bucket"):
-                        st.wait_bucket(bi)
-                    lo, hi = st.bucket_range(bi)
-                    self.opt.update(lo, hi, grad_scale=1.0 / self.dp)
-                st.reset_buckets()
-            return acc.get("loss")
-        if isinstance(st, DDPStore):
-            with mark("comm:finish_grads"):
-                st.finish_grads()
-        with mark("optim"):
-            return self._optim(acc)
+        self._finish_and_step()
+        return acc.get("loss")
 
     def _zb_costs(self, S):
         """Per-stage (F, B, W) costs of the zero-bubble simulation: the same on every rank (model
@@ -254,27 +236,6 @@ class PipelineEngine(Engine):
         if self._cost_cache.get(key) is None:
             self._cost_cache[key] = tuple(stage_costs(self.model, S, self.groups))
         return self._cost_cache[key]
-
-    def _optim(self, acc):
-        kw = {}
-        if self.scaler is not None:
-            # every stage holds different gradients: one skip decision for the whole job
-            self.scaler.check(self.opt.grad)
-            self.scaler.reduce_flag(None)
-            kw = self.scaler.opt_kwargs(self.opt)
-        if self.clipper is not None:
-            # the stages hold disjoint units (no weight is tied across stages), so the global norm
-            # sums the stages' squares over the pipeline group; with PP x DP the replica
-            # all-reduce has already made a stage's gradients identical across its replicas
-            cl = self.clipper
-            cl.begin()
-            cl.add(self.opt.grad, replicated=False)
-            cl.reduce(self.pp_tp)
-            kw.update(cl.finish(1.0 / self.dp, kw.get("grad_scale_t")))
-        self.opt.step(grad_scale=1.0 / self.dp, **kw)
-        if self.scaler is not None:
-            self.scaler.update()
-        return acc.get("loss")
 
     @torch.no_grad()
     def eval_step(self, batch, targets):

@@ -27,6 +27,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from ..utils.profiling import mark
 from .store import LocalStore
 from .transport import Transport, make_transport
 
@@ -98,44 +99,31 @@ class DDPStore(LocalStore):
         if self.overlap and self._ready[bi] >= self.accum_steps * len(self.buckets[bi]):
             self._launch(bi)  # (once: _launch skips a bucket already in flight)
 
-    def bucket_range(self, bi):
-        return self._range(bi)
-
-    def launch_all(self):
-        """Enqueue every bucket not launched yet (overlap off, or buckets left partial)."""
-        if self.tp.active:
-            for bi in range(len(self.buckets)):
-                self._launch(bi)
-
-    def wait_bucket(self, bi):
-        """Order the current stream after bucket ``bi``'s all-reduce (no host sync)."""
-        if self.tp.active:
-            self._works[bi].wait()
-            if bi in self._tmp:
-                lo, hi = self._range(bi)
-                self.grads[lo:hi].copy_(self._tmp[bi])
-
-    def reset_buckets(self):
-        self._works.clear()
-        self._tmp.clear()
-        self._ready = [0] * len(self.buckets)
-
     def reset_step_state(self):
-        self.reset_buckets()
-
-    def finish_grads(self):
-        """Wait for every bucket (launching any not yet launched, e.g. overlap off)."""
-        if self.tp.active:
-            for bi in range(len(self.buckets)):
-                self._launch(bi)
-            for bi in range(len(self.buckets)):
-                self._works[bi].wait()
-                if bi in self._tmp:
-                    lo, hi = self._range(bi)
-                    self.grads[lo:hi].copy_(self._tmp[bi])
         self._works.clear()
         self._tmp.clear()
         self._ready = [0] * len(self.buckets)
+
+    def finish_grads(self, ready=None):
+        """Complete the step's all-reduces: every bucket not launched yet (overlap off, or left
+        partial) is enqueued, then bucket by bucket, in launch order, the current stream is
+        ordered after its all-reduce (no host sync), a reduce-dtype temporary is copied back and
+        ``ready(lo, hi)`` hears of the bucket's range -- AdamW of the buckets already reduced can
+        run while the last ones (the embeddings, whose backward comes last) are still on the comm
+        stream.  An inactive transport reports the whole buffer once, as ``LocalStore`` does."""
+        if not self.tp.active:
+            return super().finish_grads(ready)
+        for bi in range(len(self.buckets)):
+            self._launch(bi)
+        for bi in range(len(self.buckets)):
+            with mark("comm:wait_bucket"):
+                self._works[bi].wait()
+            lo, hi = self._range(bi)
+            if bi in self._tmp:
+                self.grads[lo:hi].copy_(self._tmp[bi])
+            if ready is not None:
+                ready(lo, hi)
+        self.reset_step_state()
 
     @property
     def grad_scale(self) -> float:

@@ -290,51 +290,28 @@ class FSDPStore(ParamStore):
         self._fresh.discard(u)
         # g is dropped here: the transport keeps it alive until the collective has read it
 
-    def finish_grads(self):
-        rep_w = None
-        if self.sharded:
-            rep_w = self.tp.all_reduce(self.rep_grads, async_op=True)
-        for u, lst in sorted(self._rs.items()):
-            for w, tmp in lst:
-                w.wait()
+    def finish_grads(self, ready=None):
+        """Complete the step's gradient collectives; ``ready(lo, hi)`` hears of each unit's range
+        of the shard buffer as soon as it is final (``LocalStore.finish_grads`` has the contract).
+        Units are waited for in the order their reduce-scatters were issued, the last unit first
+        (the per-unit adds are independent: the order does not change the gradients), so AdamW of
+        the units already reduce-scattered can run on the compute stream while the earlier units'
+        reduce-scatters are still on the comm stream.  ``rep_grads`` is final on return."""
+        rep_w = self.tp.all_reduce(self.rep_grads, async_op=True) if self.sharded else None
+        # (units without a reduce-scatter this step -- one rank, or no gradient -- come last)
+        for u in sorted(self._rs, reverse=True) + [u for u in self.units if u not in self._rs]:
+            for w, tmp in self._rs.get(u, ()):
+                with mark("comm:wait_unit"):
+                    w.wait()
                 if tmp is not None:
                     self.shard(self.grads, u).add_(tmp.float())
+            if ready is not None:
+                ready(self.shard_off[u], self.shard_off[u] + self.shard_len[u])
         self._rs.clear()
         if rep_w is not None:
             rep_w.wait()
         self._in_backward = False
         # anything still gathered from the forward (e.g. the head) is released now
-        for u in list(self._full):
-            self._release(u)
-
-    def finish_grads_and_update(self, opt, opt_rep, grad_scale: float = 1.0):
-        """``finish_grads`` + both AdamW steps, unit by unit: each unit's shard is updated as
-        soon as its reduce-scatter has landed (units complete in backward order, the last
-        layer's first), while the earlier units' reduce-scatters are still on the comm stream --
-        as the DDP engine does bucket by bucket.  Only the last units' reduce-scatters remain on
-        the critical path.  Same arithmetic as ``finish_grads`` then ``opt.step`` (AdamW is
-        element-wise; the step count advances once)."""
-        rep_w = self.tp.all_reduce(self.rep_grads, async_op=True) if self.sharded else None
-        opt.begin_step()
-        done = set()
-        for u in sorted(self._rs, reverse=True):  # (reduce-scatters were issued last unit first)
-            for w, tmp in self._rs[u]:
-                with mark("comm:wait_unit"):
-                    w.wait()
-                if tmp is not None:
-                    self.shard(self.grads, u).add_(tmp.float())
-            lo = self.shard_off[u]
-            opt.update(lo, lo + self.shard_len[u], grad_scale=grad_scale)
-            done.add(u)
-        for u in self.units:  # (a unit without a reduce-scatter this step: one rank, or no grad)
-            if u not in done:
-                lo = self.shard_off[u]
-                opt.update(lo, lo + self.shard_len[u], grad_scale=grad_scale)
-        self._rs.clear()
-        if rep_w is not None:
-            rep_w.wait()
-        opt_rep.step(grad_scale=grad_scale)
-        self._in_backward = False
         for u in list(self._full):
             self._release(u)
 
@@ -369,11 +346,6 @@ class FSDPStore(ParamStore):
             sh = self.shard(flat_shards, u).to(self.device).contiguous()
             if not self.sharded:
                 full = sh
-            elif not getattr(self.tp, "p2p", True):  # (a transport without point-to-point: all-gather)
-                full = torch.empty(self.unit_len[u], dtype=sh.dtype, device=self.device)
-                self.tp.all_gather(full, sh)
-                if self.rank != dst_rank:
-                    continue
             elif self.rank == dst_rank:
                 # gathered to dst_rank ONLY (grouped point-to-point): the reference's
                 # FULL_STATE_DICT all-gathers every unit onto every rank (main-fsdp.py:193-194),

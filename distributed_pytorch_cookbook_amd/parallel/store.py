@@ -172,6 +172,14 @@ class LocalStore(ParamStore):
     def zero_grad(self):
         self.grads.zero_()
 
+    def finish_grads(self, ready=None):
+        """Complete the step's gradient collectives (none here).  Every store has this method:
+        ``ready(lo, hi)`` is called for each range of the optimizer's flat gradient buffer as soon
+        as it is final.  The ranges are disjoint, tile ``[0, numel)`` exactly once per step, and
+        every ``lo`` and ``hi - lo`` is a multiple of 4 (``FlatAdamW.update``'s kernel path)."""
+        if ready is not None:
+            ready(0, self.numel)
+
     def named_entries(self):
         return [(e.name, e) for e in self.entries]
 

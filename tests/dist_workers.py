@@ -302,14 +302,12 @@ class _FailingCapture:
 
     def __enter__(self):
         st = self.eng.store
-        tgt = st if hasattr(st, "finish_grads") and getattr(st, "tp", None) is not None else self.eng.p2p
-        # FSDP's unit-wise path (finish_grads_and_update) and the bucket-by-bucket AdamW of DDP /
-        # PP x DP (wait_bucket) fail at the same point
-        names = ["finish_grads", "finish_grads_and_update", "wait_bucket"] if tgt is st else ["drain"]
-        for name in names:
-            if hasattr(tgt, name):
-                self.saved.append((tgt, name))
-                setattr(tgt, name, self._boom)
+        # a store with a transport fails where its collectives are completed (every engine's end
+        # of step, overlapped with AdamW or not, goes through finish_grads); a pipeline without
+        # replicas where its sends are drained
+        tgt, name = (st, "finish_grads") if getattr(st, "tp", None) is not None else (self.eng.p2p, "drain")
+        self.saved.append((tgt, name))
+        setattr(tgt, name, self._boom)
         return self
 
     def __exit__(self, *exc):

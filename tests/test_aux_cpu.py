@@ -156,14 +156,14 @@ def test_pipeline_default_microbatches_divide_the_batch():
     from distributed_pytorch_cookbook_amd.engine.pipeline import PipelineEngine
 
     f = PipelineEngine._micro_count
-    assert f(SimpleNamespace(n_micro_req=0, pp=3), 64) == 8
+    assert f(SimpleNamespace(n_micro_req=0, pp=3, _mfac=4), 64) == 8
     # the zero-bubble schedules: at most 2 x stages (profiles/r6_pp/)
     assert f(SimpleNamespace(n_micro_req=0, pp=8, _mfac=2), 512) == 16
-    assert f(SimpleNamespace(n_micro_req=0, pp=8), 512) == 32
-    assert f(SimpleNamespace(n_micro_req=0, pp=2), 128) == 8
-    assert f(SimpleNamespace(n_micro_req=0, pp=5), 36) == 18
-    assert f(SimpleNamespace(n_micro_req=0, pp=1), 64) == 1
-    assert f(SimpleNamespace(n_micro_req=6, pp=2), 36) == 6
+    assert f(SimpleNamespace(n_micro_req=0, pp=8, _mfac=4), 512) == 32
+    assert f(SimpleNamespace(n_micro_req=0, pp=2, _mfac=4), 128) == 8
+    assert f(SimpleNamespace(n_micro_req=0, pp=5, _mfac=4), 36) == 18
+    assert f(SimpleNamespace(n_micro_req=0, pp=1, _mfac=4), 64) == 1
+    assert f(SimpleNamespace(n_micro_req=6, pp=2, _mfac=4), 36) == 6
 
 
 def test_phase_ranges_cover_every_engine(monkeypatch):
@@ -171,7 +171,7 @@ def test_phase_ranges_cover_every_engine(monkeypatch):
     every engine's eager step -- recorded here by replacing the range helper."""
     import contextlib
 
-    from distributed_pytorch_cookbook_amd.engine import data_parallel, fsdp, pipeline
+    from distributed_pytorch_cookbook_amd.engine import base, data_parallel, fsdp, pipeline
     from distributed_pytorch_cookbook_amd.engine.data_parallel import DataParallelEngine
     from distributed_pytorch_cookbook_amd.engine.fsdp import FSDPEngine
     from distributed_pytorch_cookbook_amd.engine.pipeline import PipelineEngine
@@ -185,7 +185,7 @@ def test_phase_ranges_cover_every_engine(monkeypatch):
         seen.append(name)
         yield
 
-    for mod in (data_parallel, fsdp, pipeline):
+    for mod in (base, data_parallel, fsdp, pipeline):  # (base: the shared end of a step)
         monkeypatch.setattr(mod, "mark", rec)
     for build in (lambda m: DataParallelEngine(m, "cpu", lr=1e-3),
                   lambda m: FSDPEngine(m, "cpu", lr=1e-3),

@@ -91,23 +91,37 @@ def check_norms(out, world, single):
     return recs
 
 
+def engines_agree_with_single_clipped(tmp_path, single, kind, world, grad_scaler):
+    out = tmp_path / f"{kind}.pt"
+    run_workers(worker_clip, world, str(out), kind, 2, grad_scaler)
+    recs = check_norms(out, world, single)
+    assert_close_sd(torch.load(out, weights_only=True), single[0])
+    if kind == "ddp":
+        # m_s = 0.9 m_{s-1} + 0.1 coef_s g_s / W on every rank (g: the all-reduced sum; with the
+        # scaler the buffer holds 2^16 g, and two clean steps leave the scale where it starts)
+        for r in recs:
+            m = torch.zeros_like(r["rec"][0]["grads"], dtype=torch.float64)
+            for st in r["rec"]:
+                coef = MAX_NORM / (st["norm"] + 1e-6)
+                g = st["grads"].double() / (2.0 ** 16 if grad_scaler else 1.0)
+                m = 0.9 * m + 0.1 * coef * g / world
+                assert rel(st["exp_avg"], m) <= 1e-5
+
+
 @pytest.mark.slow
 @pytest.mark.parametrize("kind,world", [("ddp", 2), ("fsdp", 2), ("pipe-1f1b", 2), ("pipe-zb", 2), ("pipe_ddp", 4)])
 def test_engines_agree_with_single_clipped(tmp_path, single, kind, world):
     """Catches double-counted replicated parameters, a missing or wrong-group all-reduce of the
     squared norm, and a forgotten 1/W."""
-    out = tmp_path / f"{kind}.pt"
-    run_workers(worker_clip, world, str(out), kind, 2, False)
-    recs = check_norms(out, world, single)
-    assert_close_sd(torch.load(out, weights_only=True), single[0])
-    if kind == "ddp":
-        # m_s = 0.9 m_{s-1} + 0.1 coef_s g_s / W on every rank (g: the all-reduced sum)
-        for r in recs:
-            m = torch.zeros_like(r["rec"][0]["grads"], dtype=torch.float64)
-            for st in r["rec"]:
-                coef = MAX_NORM / (st["norm"] + 1e-6)
-                m = 0.9 * m + 0.1 * coef * st["grads"].double() / world
-                assert rel(st["exp_avg"], m) <= 1e-5
+    engines_agree_with_single_clipped(tmp_path, single, kind, world, False)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("kind,world", [("ddp", 2), ("fsdp", 2), ("pipe-1f1b", 2), ("pipe_ddp", 4)])
+def test_engines_agree_with_single_clipped_under_the_scaler(tmp_path, single, kind, world):
+    """Loss scaling and clipping together, where every engine now runs the same code: held to
+    the single (unscaled) engine by the tolerances of the test above."""
+    engines_agree_with_single_clipped(tmp_path, single, kind, world, True)
 
 
 @pytest.mark.slow

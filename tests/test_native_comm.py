@@ -105,7 +105,7 @@ def test_native_transport_ddp_hip_graph():
 def test_native_fsdp_sharded_unitwise_adamw(graph):
     """FSDP on its N > 1 code path at one rank (native RCCL communicator, sharded store): the
     reduce-scatters complete unit by unit and AdamW updates each unit's shard as its
-    reduce-scatter lands (FSDPStore.finish_grads_and_update), eager and HIP-graph captured;
+    reduce-scatter lands (FSDPStore.finish_grads feeding FlatAdamW.update), eager and HIP-graph captured;
     the rank-0 checkpoint gather goes through grouped point-to-point.  Same weights as the
     unsharded FSDP engine."""
     from distributed_pytorch_cookbook_amd.engine.fsdp import FSDPEngine
