@@ -31,7 +31,7 @@ from ..parallel.fsdp import _placeholder
 from ..parallel.pipeline import (P2P, partition, run_schedule, schedule_1f1b, schedule_gpipe, schedule_zb,
                                  stage_costs, unit_costs)
 from ..parallel.store import LocalStore
-from ..parallel.transport import TorchTransport, make_mesh_transports
+from ..parallel.transport import TorchTransport, make_mesh_transports, make_transport
 from ..utils.profiling import mark
 from .base import Engine, GraphedStep
 
@@ -52,23 +52,17 @@ class PipelineEngine(Engine):
         if pp * dp != world:
             raise ValueError(f"pp ({pp}) x dp ({dp}) must equal the world size ({world})")
         self.pp, self.dp = pp, dp
+        mesh = comm.make_mesh(pp, dp) if world > 1 else (None, None, 0, 0, [0])
+        self.pp_group, self.dp_group, self.stage, self.replica, self.pp_ranks = mesh
         if world > 1:
-            self.pp_group, self.dp_group, self.stage, self.replica, pp_ranks = comm.make_mesh(pp, dp)
             self.pp_tp, self.dp_tp = make_mesh_transports(self.pp_group, self.dp_group, self.stage,
                                                           self.replica, self.device, comm_kind)
-        elif force_dist:
-            # one rank on the N > 1 path (bench.py --force_dist_path): the replica store is the
-            # bucketed DDP store over a native 1-rank communicator (no neighbour: no p2p)
-            from ..parallel.transport import make_transport
-
-            self.pp_group = self.dp_group = None
-            self.stage, self.replica, pp_ranks = 0, 0, [0]
-            self.pp_tp = TorchTransport(None)
-            self.dp_tp = make_transport(None, self.device, "native")
         else:
-            self.pp_group = self.dp_group = None
-            self.stage, self.replica, pp_ranks = 0, 0, [0]
             self.pp_tp = self.dp_tp = TorchTransport(None)
+            if force_dist:
+                # one rank on the N > 1 path (bench.py --force_dist_path): the replica store is the
+                # bucketed DDP store over a native 1-rank communicator (no neighbour: no p2p)
+                self.dp_tp = make_transport(None, self.device, "native")
         self.dp_world = dp
         self.dp_rank = self.replica
         self.first = self.stage == 0
@@ -117,7 +111,6 @@ class PipelineEngine(Engine):
         # from its last micro-batch's backward -- or W -- passes, unit by unit)
         self.may_overlap = self.dp_tp.active and (dp > 1 or force_dist)  # (the store rides dp_tp)
         self.p2p = P2P(self.pp_tp, self.stage, pp, self.device, wire_dtype=wire_dtype)
-        self.pp_ranks = pp_ranks
         self.D = model.dim
         assert nunits == len(model.units())
         if world > 1:
@@ -173,6 +166,16 @@ class PipelineEngine(Engine):
 
     def _act_shape(self, mb, S):
         return (mb * S, self.D)
+
+    def _relay(self, shape, run):
+        """One blocking pass through this stage outside a schedule (evaluation, generation):
+        receive the boundary tensor unless first stage, ``run(x)``, send the result on unless
+        last stage.  Returns what ``run`` returned."""
+        x, _ = self.p2p.exchange(recv_prev_shape=None if self.first else shape)
+        out = run(x)
+        if not self.last:
+            self.p2p.exchange(send_next=out)
+        return out
 
     # ------------------------------------------------------------------ training
     def _step_body(self, batch, targets):
@@ -244,15 +247,12 @@ class PipelineEngine(Engine):
         shape = self._act_shape(mb, S)
         tot = [torch.zeros((), device=self.device) for _ in range(3)]
         for m in range(self.n_micro):
-            x, _ = self.p2p.exchange(recv_prev_shape=None if self.first else shape)
-            out = self._fwd(micro[m], x, False, want_correct=True)
+            out = self._relay(shape, lambda x: self._fwd(micro[m], x, False, want_correct=True))
             if self.last:
                 loss, n_valid, n_corr = out
                 tot[0] = tot[0] + loss * n_valid
                 tot[1] = tot[1] + n_valid
                 tot[2] = tot[2] + n_corr
-            else:
-                self.p2p.exchange(send_next=out)
         return tot if self.last else None
 
     # ------------------------------------------------------------------ generation
@@ -264,18 +264,18 @@ class PipelineEngine(Engine):
             from ..models.fused import head_logits, last_rows
 
             N, S = input_ids.shape
-            shape = (N * S, eng.D)
-            x, _ = eng.p2p.exchange(recv_prev_shape=None if eng.first else shape)
             st = eng.store
-            if eng.first:
-                x = run_embeddings(eng.model, st, input_ids, position_ids, False)
-            x = run_layers(eng.model, st, x, None, N, S, eng.layers, False)  # (output formed here)
+
+            def layers(x):
+                if eng.first:
+                    x = run_embeddings(eng.model, st, input_ids, position_ids, False)
+                return run_layers(eng.model, st, x, None, N, S, eng.layers, False)  # (output formed here)
+
+            x = eng._relay(eng._act_shape(N, S), layers)
             V = eng.model.vocab_size
             tok = torch.zeros(1, dtype=torch.int64, device=eng.device)
             if eng.last:
                 tok[0] = head_logits(eng.model, last_rows(x, N, S), st)[0].argmax()
-            else:
-                eng.p2p.exchange(send_next=x)
             if eng.pp > 1:
                 eng.pp_tp.broadcast(tok, src=eng.pp - 1)
             out = torch.zeros(1, 1, V, device=eng.device)

@@ -19,6 +19,11 @@ receive only where it consumes it; the executed order is exactly ``schedule_1f1b
 ``schedule_gpipe`` / ``schedule_zb`` (``run_schedule``); the key-padding mask and targets are
 NOT sent -- every stage of a replica reads the same batch from its own loader.
 
+Which sends and which receive share a group is stated once, in ``exchange_plan``: the executor
+(``run_schedule``) posts that plan group by group, and the deadlock checker
+(``p2p_deadlock_free``) matches the same plan's groups across stages under RCCL's blocking
+semantics -- so what the checker approves is what runs.
+
 Zero-bubble schedule (``schedule_zb``, Qi et al. 2023 "Zero Bubble Pipeline Parallelism",
 the H1 family): a micro-batch's backward is split into B -- the input-gradient chain, what the
 previous stage waits for -- and W -- the weight-gradient GEMMs (and the embedding scatter),
@@ -32,7 +37,7 @@ relative order is 1F1B's.  HBM is plentiful on MI355X (288 GB), so a stage may h
 from __future__ import annotations
 
 import functools
-import heapq
+from typing import NamedTuple
 
 import torch
 
@@ -46,22 +51,34 @@ import torch
 _GEMM_RATE, _ATTN_RATE, _MEM_RATE = 1.0e15, 0.4e15, 5.0e12
 
 
+def _work_terms(model, seq_len: int):
+    """Per-token work of a layer and the head as exact integers -- (projection forward FLOPs,
+    attention forward FLOPs, layer bytes, LM-head forward FLOPs, bytes of one pass over the bf16
+    logits, norm_out bytes) -- the one statement ``unit_costs`` and ``stage_costs`` share.  Each
+    divides by the rates itself, in its own operation order: the floats they return decide ties
+    in ``partition`` and ``simulate_orders`` and must keep their bits."""
+    D = model.dim
+    hd = model.heads * model.head_dim
+    V = model.vocab_size
+    gemm = 2 * (3 * D * hd + hd * D + 2 * 4 * D * D)  # forward FLOPs of the layer's projections
+    attn = 2 * seq_len * hd  # causal: QK^T + PV over S / 2 keys on average
+    layer_bytes = 32 * D + 4 * 4 * D  # two LayerNorms fwd + bwd, residual / bias / act' passes
+    return gemm, attn, layer_bytes, 2 * D * V, 2 * V, 16 * D
+
+
 def unit_costs(model, seq_len: int) -> list[float]:
     """Estimated seconds per token of one training step (forward + backward) for each unit
     (embeddings, layers..., head) -- the stage balance of ``partition``.  Counts the backward
     and the memory-bound passes, not only forward FLOPs: at GPT-2 small the head (LM-head GEMM
     + the cross-entropy over V logits) comes out at ~4.4 layers, at GPT-2 medium ~3.5."""
-    D = model.dim
-    hd = model.heads * model.head_dim
-    V = model.vocab_size
-    S = seq_len
-    gemm = 2 * (3 * D * hd + hd * D + 2 * 4 * D * D)  # forward FLOPs of the layer's projections
-    attn = 2 * S * hd  # causal: QK^T + PV over S / 2 keys on average
-    layer_bytes = 32 * D + 4 * 4 * D  # two LayerNorms fwd + bwd, residual / bias / act' passes
+    gemm, attn, layer_bytes, head_gemm, logit_bytes, norm_bytes = _work_terms(model, seq_len)
     layer = 3 * gemm / _GEMM_RATE + 3.5 * attn / _ATTN_RATE + layer_bytes / _MEM_RATE
     # head: LM-head GEMM (3 x), the fused cross-entropy (read + write the bf16 logits), norm_out
-    head = 3 * 2 * D * V / _GEMM_RATE + (4 * V + 16 * D) / _MEM_RATE
-    emb = (4 * 4 * D + 64) / _MEM_RATE  # gather-add forward, sorted segment-sum backward
+    head = 3 * head_gemm / _GEMM_RATE + (2 * logit_bytes + norm_bytes) / _MEM_RATE
+    # gather-add forward, sorted segment-sum backward: 16 D + 64 bytes here, 4 D + (8 D + 64) in
+    # ``stage_costs``.  The two disagree; reconciling them could move a stage boundary, so both
+    # stay as they are
+    emb = (4 * 4 * model.dim + 64) / _MEM_RATE
     return [emb] + [layer] * model.num_layers + [head]
 
 
@@ -170,66 +187,91 @@ class Recv:
         return self.buf if self.buf.dtype == self.dtype else self.buf.to(self.dtype)
 
 
-def run_schedule(order, first: bool, last: bool, forward, backward, p2p: "P2P", shape, wgrad=None):
-    """Execute a stage's schedule -- a list of ('F', m) / ('B', m) from ``schedule_1f1b`` or
-    ``schedule_gpipe``, plus ('W', m) from ``schedule_zb`` (``wgrad(m)``: the deferred weight
-    gradients of micro-batch m; no communication) -- with asynchronous grouped p2p.
+class Exchange(NamedTuple):
+    """One grouped exchange of a stage: each field is None or the ('F' | 'B', m) op it serves."""
+    send_next: tuple | None = None  # this op's output, to the next stage
+    send_prev: tuple | None = None  # this op's input gradient, to the previous stage
+    recv_prev: tuple | None = None  # the later op that consumes what the previous stage sends
+    recv_next: tuple | None = None  # the later op that consumes what the next stage sends
 
-    Rule: before the first op its receive is posted; after every op ONE grouped exchange is
-    posted holding that op's send (y_m to the next stage, dx_m to the previous) and the
-    receive the NEXT op will consume (x from the previous stage for an F, g from the next
-    for a B).  Every exchange is issued in schedule order on both sides of a link, so the
-    comm streams see the same group sequence the blocking PipeDream-flush loop issues --
-    deadlock-free -- while the compute stream waits only where a received tensor is used.
-    ``forward(m, x) -> y`` (None on the last stage), ``backward(m, g) -> dx`` (None on the
-    first stage)."""
+
+def exchange_plan(order, first: bool, last: bool) -> list[Exchange]:
+    """The grouped exchanges a stage posts for ``order``: ``len(order) + 1`` groups, group 0
+    before the first op and group i + 1 after op i; a group with every field None posts nothing.
+    ``run_schedule`` executes this plan and ``p2p_deadlock_free`` checks it: there is no other
+    statement of the rule.
+
+    Rule: the first op's receive goes alone into group 0; after every op ONE group holds that
+    op's send (y_m to the next stage, dx_m to the previous) and the receive of the next op that
+    communicates (x from the previous stage for an F, g from the next for a B), W passes in
+    between or not: a send-only group followed by a receive-only group on both sides of a link
+    deadlocks under RCCL's blocking sends."""
 
     def need(op):
-        kind, _ = op
-        if kind == "F":
-            return (shape, None) if not first else (None, None)
-        if kind == "W":
-            return (None, None)
-        return (None, shape) if not last else (None, None)
+        """(recv_prev, recv_next) of the exchange that feeds ``op``."""
+        if op[0] == "F" and not first:
+            return op, None
+        if op[0] == "B" and not last:
+            return None, op
+        return None, None
 
-    pending = None  # the Recv the next op consumes
-    rp, rn = need(order[0]) if order else (None, None)
-    if rp is not None or rn is not None:
-        a, b = p2p.post(recv_prev_shape=rp, recv_next_shape=rn)
-        pending = a or b
-    for i, (kind, m) in enumerate(order):
-        if kind == "W":
-            wgrad(m)
-            send_next = send_prev = None
-        elif kind == "F":
-            x = pending.get() if (pending is not None and not first) else None
-            out = forward(m, x)
-            send_next, send_prev = (out if not last else None), None
-        else:
-            g = pending.get() if (pending is not None and not last) else None
-            dx = backward(m, g)
-            send_next, send_prev = None, (dx if not first else None)
-        if kind != "W":  # (a W consumes nothing: a receive posted before it stays pending)
-            pending = None
-        rp = rn = None
-        # the receive of the next op that communicates goes into THIS op's group, W passes in
-        # between or not: a send-only group followed by a receive-only group on both sides of a
-        # link deadlocks under RCCL's blocking sends (p2p_deadlock_free)
+    plan = [Exchange(None, None, *(need(order[0]) if order else (None, None)))]
+    pending = any(plan[0])  # a receive is posted that no op has consumed yet
+    for i, op in enumerate(order):
+        if op[0] != "W":  # (a W consumes nothing: a receive posted before it stays pending)
+            pending = False
         j = i + 1
         while j < len(order) and order[j][0] == "W":
             j += 1
-        if j < len(order) and pending is None:
-            rp, rn = need(order[j])
-        if send_next is not None or send_prev is not None or rp is not None or rn is not None:
-            a, b = p2p.post(send_next=send_next, send_prev=send_prev, recv_prev_shape=rp,
-                            recv_next_shape=rn)
-            pending = a or b
+        rp, rn = need(order[j]) if j < len(order) and not pending else (None, None)
+        plan.append(Exchange(op if op[0] == "F" and not last else None,
+                             op if op[0] == "B" and not first else None, rp, rn))
+        pending = pending or rp is not None or rn is not None
+    return plan
+
+
+def run_schedule(order, first: bool, last: bool, forward, backward, p2p: "P2P", shape, wgrad=None):
+    """Execute a stage's schedule -- a list of ('F', m) / ('B', m) from ``schedule_1f1b`` or
+    ``schedule_gpipe``, plus ('W', m) from ``schedule_zb`` (``wgrad(m)``: the deferred weight
+    gradients of micro-batch m; no communication) -- with the asynchronous grouped p2p of
+    ``exchange_plan``.
+
+    Every exchange is issued in schedule order on both sides of a link, so the comm streams see
+    the same group sequence the blocking PipeDream-flush loop issues -- deadlock-free -- while
+    the compute stream waits only where a received tensor is used.
+    ``forward(m, x) -> y`` (None on the last stage), ``backward(m, g) -> dx`` (None on the
+    first stage)."""
+    plan = exchange_plan(order, first, last)
+    inbox = {}  # op -> the Recv it consumes, from the group that posted it
+
+    def post(g, out=None):
+        if any(g):
+            a, b = p2p.post(send_next=out if g.send_next else None, send_prev=out if g.send_prev else None,
+                            recv_prev_shape=shape if g.recv_prev else None,
+                            recv_next_shape=shape if g.recv_next else None)
+            if g.recv_prev:
+                inbox[g.recv_prev] = a
+            if g.recv_next:
+                inbox[g.recv_next] = b
+
+    post(plan[0])
+    for op, g in zip(order, plan[1:]):
+        kind, m = op
+        r = inbox.pop(op, None)
+        x = r.get() if r is not None else None
+        if kind == "W":
+            out = wgrad(m)
+        else:
+            out = forward(m, x) if kind == "F" else backward(m, x)
+        post(g, out)
     p2p.drain()
 
 
-def schedule_1f1b(n_micro: int, stage: int, n_stages: int):
-    """List of ('F', m) / ('B', m) in execution order for one stage (PipeDream-flush)."""
-    warm = min(n_stages - stage - 1, n_micro)
+def schedule_1f1b(n_micro: int, stage: int, n_stages: int, warm: int | None = None):
+    """List of ('F', m) / ('B', m) in execution order for one stage: ``warm`` forwards before the
+    first backward (default stages - stage - 1, PipeDream-flush; clamped to [0, n_micro]), then
+    one forward one backward."""
+    warm = min(max(n_stages - stage - 1 if warm is None else warm, 0), n_micro)
     order = [("F", m) for m in range(warm)]
     f, b = warm, 0
     while f < n_micro:
@@ -253,45 +295,18 @@ def stage_costs(model, seq_len: int, groups) -> list[tuple[float, float, float]]
     input-gradient chain (dgrad GEMMs, the attention backward ~2.5 x its forward, the memory
     passes), W the weight-gradient GEMMs (the LM head's included: the largest single product of
     the last stage) and the embedding scatter."""
+    gemm, attn, layer_bytes, head_gemm, logit_bytes, norm_bytes = _work_terms(model, seq_len)
     D = model.dim
-    hd = model.heads * model.head_dim
-    V = model.vocab_size
-    S = seq_len
-    g = 2 * (3 * D * hd + hd * D + 2 * 4 * D * D) / _GEMM_RATE
-    a = 2 * S * hd / _ATTN_RATE
-    mem = (32 * D + 4 * 4 * D) / _MEM_RATE
-    per_unit = {}
+    g = gemm / _GEMM_RATE
+    a = attn / _ATTN_RATE
+    mem = layer_bytes / _MEM_RATE
+    hg = head_gemm / _GEMM_RATE
     L = model.num_layers
-    for u in range(L + 2):
-        if u == 0:
-            per_unit[u] = (4 * D / _MEM_RATE, 0.0, (8 * D + 64) / _MEM_RATE)
-        elif u == L + 1:
-            hg = 2 * D * V / _GEMM_RATE
-            per_unit[u] = (hg + 2 * V / _MEM_RATE, hg + (2 * V + 16 * D) / _MEM_RATE, hg)
-        else:
-            per_unit[u] = (g + a + 0.4 * mem, g + 2.5 * a + 0.6 * mem, g)
+    # (the embeddings: 4 D + (8 D + 64) bytes here, 16 D + 64 in ``unit_costs``; left as it is)
+    per_unit = ([(4 * D / _MEM_RATE, 0.0, (8 * D + 64) / _MEM_RATE)]
+                + [(g + a + 0.4 * mem, g + 2.5 * a + 0.6 * mem, g)] * L
+                + [(hg + logit_bytes / _MEM_RATE, hg + (logit_bytes + norm_bytes) / _MEM_RATE, hg)])
     return [tuple(sum(per_unit[u][k] for u in grp) for k in range(3)) for grp in groups]
-
-
-def fb_order(n_micro: int, stage: int, n_stages: int, warm: int | None = None):
-    """1F1B's F / B order for one stage with ``warm`` forwards before the first backward (default
-    stages - stage - 1, PipeDream-flush)."""
-    w = n_stages - stage - 1 if warm is None else warm
-    return [op for op in schedule_1f1b_w(n_micro, min(max(w, 0), n_micro))]
-
-
-def schedule_1f1b_w(n_micro: int, warm: int):
-    order = [("F", m) for m in range(warm)]
-    f, b = warm, 0
-    while f < n_micro:
-        order.append(("F", f))
-        f += 1
-        order.append(("B", b))
-        b += 1
-    while b < n_micro:
-        order.append(("B", b))
-        b += 1
-    return order
 
 
 def simulate_orders(n_micro: int, costs, wmax=None, comm: float = 0.0, split_w: bool = True, warm=None):
@@ -310,7 +325,7 @@ def simulate_orders(n_micro: int, costs, wmax=None, comm: float = 0.0, split_w: 
     p = len(costs)
     if wmax is None:
         wmax = [p] * p
-    fbs = [fb_order(n_micro, s, p, None if warm is None else warm[s]) for s in range(p)]
+    fbs = [schedule_1f1b(n_micro, s, p, warm=None if warm is None else warm[s]) for s in range(p)]
     INF = float("inf")
     t = [0.0] * p
     nxt = [0] * p  # index of the stage's next F / B op
@@ -408,44 +423,19 @@ def bubble_factor(n_micro: int, costs, schedule: str = "zb", comm: float = 0.0) 
 
 def p2p_deadlock_free(orders) -> bool:
     """Check a set of per-stage orders against RCCL's point-to-point semantics as
-    ``run_schedule`` issues them: after op i one group holding op i's send and the receive the
-    next communicating op consumes (the first op's receive alone before it); a group completes only when every
-    send in it has been matched by the peer's receive in the peer's CURRENT group and every
-    receive by the peer's send.  True when every stage runs to the end."""
+    ``run_schedule`` issues them -- the non-empty groups of each stage's ``exchange_plan``: a
+    group completes only when every send in it has been matched by the peer's receive in the
+    peer's CURRENT group and every receive by the peer's send.  True when every stage runs to
+    the end."""
     p = len(orders)
-    groups = []
-    for s, order in enumerate(orders):
-        first, last = s == 0, s == p - 1
 
-        def need(op):
-            if op[0] == "F":
-                return None if first else ("recv", s - 1, ("F", op[1]))
-            if op[0] == "B":
-                return None if last else ("recv", s + 1, ("B", op[1]))
-            return None
+    def messages(s, g):
+        msgs = (("send", s + 1, g.send_next), ("send", s - 1, g.send_prev),
+                ("recv", s - 1, g.recv_prev), ("recv", s + 1, g.recv_next))
+        return [msg for msg in msgs if msg[2] is not None]
 
-        gs = []
-        pend = need(order[0]) if order else None  # (a schedule never starts with a W)
-        if pend:
-            gs.append([pend])
-        for i, op in enumerate(order):
-            g = []
-            if op[0] == "F" and not last:
-                g.append(("send", s + 1, ("F", op[1])))
-            if op[0] == "B" and not first:
-                g.append(("send", s - 1, ("B", op[1])))
-            if op[0] != "W":
-                pend = None
-            j = i + 1
-            while j < len(order) and order[j][0] == "W":
-                j += 1
-            if j < len(order) and pend is None:
-                pend = need(order[j])
-                if pend:
-                    g.append(pend)
-            if g:
-                gs.append(g)
-        groups.append(gs)
+    groups = [[messages(s, g) for g in exchange_plan(order, s == 0, s == p - 1) if any(g)]
+              for s, order in enumerate(orders)]
     cur = [0] * p
     left = [set(range(len(groups[s][0]))) if groups[s] else set() for s in range(p)]
     progress = True

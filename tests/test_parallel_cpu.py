@@ -14,6 +14,32 @@ from distributed_pytorch_cookbook_amd.parallel.pipeline import partition, schedu
 pytestmark = pytest.mark.slow
 
 
+class RecP2P:
+    """Stands in for ``P2P`` under ``run_schedule``: no communication, records every ``post`` --
+    ``posts``: which fields were given; ``calls``: the arguments themselves.  A receive it hands
+    out yields ``(index of the post that returned it, "prev" | "next")``."""
+
+    class R:
+        def __init__(self, tag):
+            self.tag = tag
+
+        def get(self):
+            return self.tag
+
+    def __init__(self):
+        self.posts, self.calls = [], []
+
+    def post(self, **kw):
+        self.posts.append({k: v is not None for k, v in kw.items()})
+        self.calls.append(kw)
+        n = len(self.calls) - 1
+        rp, rn = kw.get("recv_prev_shape"), kw.get("recv_next_shape")
+        return (self.R((n, "prev")) if rp is not None else None), (self.R((n, "next")) if rn is not None else None)
+
+    def drain(self):
+        pass
+
+
 def assert_close_sd(a, b, atol=2e-5):
     assert list(a.keys()) == list(b.keys())
     for k in a:
@@ -149,22 +175,6 @@ def test_run_schedule_is_the_tested_schedule():
     executor calls on a 4-stage pipeline (no communication: a recording P2P)."""
     from distributed_pytorch_cookbook_amd.parallel.pipeline import run_schedule, schedule_1f1b, schedule_gpipe
 
-    class RecP2P:
-        def __init__(self):
-            self.posts = []
-
-        def post(self, **kw):
-            self.posts.append({k: v is not None for k, v in kw.items()})
-
-            class R:
-                def get(self_):
-                    return torch.zeros(1)
-            rp, rn = kw.get("recv_prev_shape"), kw.get("recv_next_shape")
-            return (R() if rp is not None else None), (R() if rn is not None else None)
-
-        def drain(self):
-            pass
-
     for sched in (schedule_1f1b, schedule_gpipe):
         for st in range(4):
             order = sched(8, st, 4)
@@ -241,33 +251,31 @@ def test_zero_bubble_orders():
     deadlock-free under RCCL's blocking p2p as run_schedule issues
     it (p2p_deadlock_free, which 1F1B / GPipe also pass); and a smaller modelled bubble than
     1F1B under the cost model -- at PP = 8, M = 32 within 10 % of the bubble-free time."""
-    from distributed_pytorch_cookbook_amd.parallel.pipeline import (bubble_factor, fb_order, p2p_deadlock_free,
+    from distributed_pytorch_cookbook_amd.parallel.pipeline import (bubble_factor, p2p_deadlock_free,
                                                                     schedule_gpipe, schedule_zb)
 
     for p, M, c, mem in itertools.product((2, 3, 4, 8), (1, 2, 3, 8, 16), ((1.0, 1.0, 1.0), (1.0, 1.4, 1.0), (0.5, 2.0, 1.5)),
                                           (1, 2)):
-        if True:
-            if True:
-                orders = [schedule_zb(M, s, p, costs=[c] * p, mem=mem) for s in range(p)]
-                for s, o in enumerate(orders):
-                    for kind in "FBW":
-                        assert [m for k, m in o if k == kind] == list(range(M)), (p, M, s, kind)
-                    pos = {op: i for i, op in enumerate(o)}
-                    assert all(pos[("F", m)] < pos[("B", m)] < pos[("W", m)] for m in range(M))
-                    # 1F1B's activation bound: at most (stages - stage) micro-batches between F and B
-                    inflight = mx = 0
-                    for k, _ in o:
-                        inflight += 1 if k == "F" else (-1 if k == "B" else 0)
-                        mx = max(mx, inflight)
-                    assert mx <= mem * (p - s), (p, M, s, mx)
-                    # the F / B order is 1F1B's (mem 2: with twice the warm-up forwards)
-                    want = schedule_1f1b(M, s, p) if mem == 1 else fb_order(M, s, p, 2 * (p - s) - 1)
-                    assert [op for op in o if op[0] != "W"] == want, (p, M, s, mem)
-                assert p2p_deadlock_free(orders), (p, M, c, mem)
-                assert p2p_deadlock_free([schedule_1f1b(M, s, p) for s in range(p)])
-                assert p2p_deadlock_free([schedule_gpipe(M, s, p) for s in range(p)])
+        orders = [schedule_zb(M, s, p, costs=[c] * p, mem=mem) for s in range(p)]
+        for s, o in enumerate(orders):
+            for kind in "FBW":
+                assert [m for k, m in o if k == kind] == list(range(M)), (p, M, s, kind)
+            pos = {op: i for i, op in enumerate(o)}
+            assert all(pos[("F", m)] < pos[("B", m)] < pos[("W", m)] for m in range(M))
+            # 1F1B's activation bound: at most (stages - stage) micro-batches between F and B
+            inflight = mx = 0
+            for k, _ in o:
+                inflight += 1 if k == "F" else (-1 if k == "B" else 0)
+                mx = max(mx, inflight)
+            assert mx <= mem * (p - s), (p, M, s, mx)
+            # the F / B order is 1F1B's (mem 2: with twice the warm-up forwards)
+            want = schedule_1f1b(M, s, p) if mem == 1 else schedule_1f1b(M, s, p, warm=2 * (p - s) - 1)
+            assert [op for op in o if op[0] != "W"] == want, (p, M, s, mem)
+        assert p2p_deadlock_free(orders), (p, M, c, mem)
+        assert p2p_deadlock_free([schedule_1f1b(M, s, p) for s in range(p)])
+        assert p2p_deadlock_free([schedule_gpipe(M, s, p) for s in range(p)])
     # 1F1B with three times the warm-up forwards is NOT deadlock-free under grouped blocking p2p
-    assert not p2p_deadlock_free([fb_order(8, s, 4, 3 * (4 - s) - 1) for s in range(4)])
+    assert not p2p_deadlock_free([schedule_1f1b(8, s, 4, warm=3 * (4 - s) - 1) for s in range(4)])
     # the checker does catch a mis-ordered exchange: stage 0 expects B1 before B0
     bad = [[("F", 0), ("F", 1), ("B", 1), ("B", 0)], [("F", 0), ("B", 0), ("F", 1), ("B", 1)]]
     assert not p2p_deadlock_free(bad)
@@ -283,22 +291,6 @@ def test_run_schedule_executes_zero_bubble_order():
     """run_schedule executes a zb order op for op (W passes through ``wgrad``), posts every send
     once and each receive in the group of the op BEFORE the next communicating op."""
     from distributed_pytorch_cookbook_amd.parallel.pipeline import run_schedule, schedule_zb
-
-    class RecP2P:
-        def __init__(self):
-            self.posts = []
-
-        def post(self, **kw):
-            self.posts.append({k: v is not None for k, v in kw.items()})
-
-            class R:
-                def get(self_):
-                    return torch.zeros(1)
-            rp, rn = kw.get("recv_prev_shape"), kw.get("recv_next_shape")
-            return (R() if rp is not None else None), (R() if rn is not None else None)
-
-        def drain(self):
-            pass
 
     for st in range(4):
         order = schedule_zb(8, st, 4)
@@ -317,3 +309,77 @@ def test_run_schedule_executes_zero_bubble_order():
         run_schedule([op for op in order if op[0] != "W"], st == 0, st == 3, lambda m, x: torch.zeros(1),
                      lambda m, g: torch.zeros(1), p2, (1,))
         assert p2p.posts == p2.posts, st
+
+
+def _sweep_stage_orders():
+    """(order, first, last) of every stage of the order sets ``test_zero_bubble_orders`` sweeps:
+    the zero-bubble orders and the 1F1B and GPipe orders of the same sizes."""
+    from distributed_pytorch_cookbook_amd.parallel.pipeline import schedule_gpipe, schedule_zb
+
+    for p, M, c, mem in itertools.product((2, 3, 4, 8), (1, 2, 3, 8, 16), ((1.0, 1.0, 1.0), (1.0, 1.4, 1.0), (0.5, 2.0, 1.5)),
+                                          (1, 2)):
+        for s in range(p):
+            yield schedule_zb(M, s, p, costs=[c] * p, mem=mem), s == 0, s == p - 1
+            yield schedule_1f1b(M, s, p), s == 0, s == p - 1
+            yield schedule_gpipe(M, s, p), s == 0, s == p - 1
+
+
+def test_run_schedule_posts_the_exchange_plan():
+    """What ``run_schedule`` posts is ``exchange_plan``, group for group and field for field: the
+    non-empty groups in order, each send carrying the output of the op the plan names, each
+    receive consumed by the op the plan names and taken from the group that posted it."""
+    from distributed_pytorch_cookbook_amd.parallel.pipeline import exchange_plan, run_schedule
+
+    shape = (3, 5)
+    n_orders = 0
+    for order, first, last in _sweep_stage_orders():
+        plan = exchange_plan(order, first, last)
+        assert len(plan) == len(order) + 1
+        p2p, seen, fed = RecP2P(), [], {}
+
+        def run(kind, m, x):
+            seen.append((kind, m))
+            fed[(kind, m)] = x
+            return (kind, m)  # the "tensor" an op produces is its own name
+
+        run_schedule(order, first, last, lambda m, x: run("F", m, x), lambda m, g: run("B", m, g), p2p, shape,
+                     wgrad=lambda m: seen.append(("W", m)))
+        assert seen == order
+        want = [g for g in plan if any(g)]
+        assert len(p2p.calls) == len(want)
+        consumers = set()
+        for n, (kw, g) in enumerate(zip(p2p.calls, want)):
+            assert set(kw) <= {"send_next", "send_prev", "recv_prev_shape", "recv_next_shape"}
+            assert kw.get("send_next") == g.send_next, (order, n)
+            assert kw.get("send_prev") == g.send_prev, (order, n)
+            assert kw.get("recv_prev_shape") == (shape if g.recv_prev else None), (order, n)
+            assert kw.get("recv_next_shape") == (shape if g.recv_next else None), (order, n)
+            if g.recv_prev:
+                assert fed[g.recv_prev] == (n, "prev"), (order, n)
+            if g.recv_next:
+                assert fed[g.recv_next] == (n, "next"), (order, n)
+            consumers.update(op for op in (g.recv_prev, g.recv_next) if op)
+        # an op for which the plan posts no receive is handed nothing
+        assert all(x is None for op, x in fed.items() if op not in consumers)
+        n_orders += 1
+    assert n_orders == 1530
+
+
+def test_deadlock_checker_reads_the_exchange_plan(monkeypatch):
+    """``p2p_deadlock_free`` has no statement of the grouping rule of its own: with one receive
+    dropped from one stage's ``exchange_plan`` a good 4-stage 1F1B set no longer passes."""
+    from distributed_pytorch_cookbook_amd.parallel import pipeline
+
+    orders = [schedule_1f1b(8, s, 4) for s in range(4)]
+    assert pipeline.p2p_deadlock_free(orders)
+    real = pipeline.exchange_plan
+
+    def drop_one_recv(order, first, last):
+        plan = real(order, first, last)
+        if not first and last:  # the last stage never asks for micro-batch 3's activations
+            n = next(i for i, g in enumerate(plan) if g.recv_prev == ("F", 3))
+            plan[n] = plan[n]._replace(recv_prev=None)
+        return plan
+
+    monkeypatch.setattr(pipeline, "exchange_plan", drop_one_recv)
+    assert not pipeline.p2p_deadlock_free(orders)
