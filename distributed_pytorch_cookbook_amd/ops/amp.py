@@ -45,10 +45,13 @@ class GradScaler:
 
     @torch.no_grad()
     def check(self, grad: torch.Tensor) -> None:
-        """found_inf |= any non-finite element of ``grad`` (flat f32 buffer, any device)."""
+        """found_inf |= any non-finite element of ``grad`` (flat f32 buffer, any device).  The
+        kernel reads 16-B vectors from the base, so a buffer whose base is not 16-B aligned (a
+        view that starts an element or three into a flat buffer) takes the torch path."""
         if grad.numel() == 0:
             return
-        if grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous() and self.found_inf.is_cuda:
+        if (grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous() and self.found_inf.is_cuda
+                and grad.data_ptr() % 16 == 0):
             _lib.call("dpc_amp_check", _lib.AmpCheckArgs(g=grad.data_ptr(), n=grad.numel(),
                                                          found_inf=self.found_inf.data_ptr()), grad.device)
             return

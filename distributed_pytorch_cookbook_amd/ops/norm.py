@@ -126,6 +126,8 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: t
             if gsum is not None:
                 gsum.add_(g.sum(0))
         return dx
+    if D % 4 or D > 2048:
+        raise ValueError("layernorm_bwd: need D % 4 == 0, D <= 2048")
     for t, nm in ((x, "x"), (dx, "dx")):
         if t.dtype != torch.float32 or t.stride(1) != 1:
             raise ValueError(f"layernorm_bwd: {nm} must be f32 with contiguous rows")

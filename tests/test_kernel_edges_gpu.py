@@ -5,6 +5,7 @@ per element against an f64 reference -- never as one norm over the whole output.
 Tolerances: ``gemm_elem_bound`` per element for the products; elsewhere a margin times the error
 an ideal kernel (the same math in plain f32 PyTorch on the same rounded inputs, rounded to the
 output dtype) makes against the same f64 reference."""
+import contextlib
 import math
 
 import pytest
@@ -13,6 +14,7 @@ import torch.nn.functional as F
 
 from kernel_checks import (GELU_LIPSCHITZ, MARGIN, MARGIN_ATTN, assert_elem_bound, assert_guards_intact,
                            assert_elem_close, assert_local_close, attention_bwd_plain, attention_plain, gemm_elem_bound, guarded)
+from mem_cases import check_cross_entropy, first_argmax
 
 from distributed_pytorch_cookbook_amd.ops import _lib
 from distributed_pytorch_cookbook_amd.ops.attention import attention_bwd, attention_fwd, decode_attention
@@ -300,9 +302,18 @@ def _seq_sum(v, start):
 
 
 def _sum_orders(v, start):
-    """The column sums of v (+ start) as plain f32 PyTorch makes them in three orders: rows first
-    to last, last to first, and torch's own reduction."""
-    return [_seq_sum(v, start), _seq_sum(v.flip(0), start), start + v.sum(0)]
+    """The column sums of v (+ start) as plain f32 PyTorch makes them in four orders: rows first
+    to last, last to first, torch's own reduction, and four rows at a time (a workgroup's rows
+    in one sweep of the row kernels) with the groups' sums added first to last.  The kernels add
+    their workgroups' sums with atomics, in an order that changes from launch to launch, and any
+    fixed order is one sample of that.  The fourth came with the cases of more than one sweep:
+    LayerNorm's gsum at T = 1026, D = 100 measured at most 1.48 x the floor of the first three in
+    60 launches and 2.00 x in one more (test_kernel_trips_gpu.py)."""
+    T = v.shape[0]
+    pad = torch.cat([v, torch.zeros((-T) % 4, *v.shape[1:], device=v.device, dtype=v.dtype)])
+    groups = pad.reshape(-1, 4, *v.shape[1:])
+    by_group = _seq_sum(((groups[:, 0] + groups[:, 1]) + groups[:, 2]) + groups[:, 3], start)
+    return [_seq_sum(v, start), _seq_sum(v.flip(0), start), start + v.sum(0), by_group]
 
 
 def _row_sum(v, order):
@@ -330,7 +341,13 @@ def _check_stats(x32, x64, mean, rstd, what):
     assert_elem_close(rstd, rstd64, rstds, MARGIN, what=what + " rstd", family="layernorm rstd", ulp_floor=True)
 
 
-LN_DIMS = [4, 100, 768, 1600]  # 4: the smallest the kernel takes (D % 4 == 0, ops/norm.py)
+# Every case of the dispatchers' switch ((D + 255) / 256, 64 lanes x 4 columns per vector, NV
+# vectors per lane).  4: the smallest the kernel takes (D % 4 == 0, ops/norm.py), NV 1; 100: NV 1
+# ragged; 260: NV 2 with one live lane in the second vector; 768: NV 3; 1024 / 1280: NV 4 / 5 full
+# (GPT-2 medium / large); 1300: NV 6 ragged; 1600: NV 7; 1796: NV 8 with one live lane in the
+# last vector; 2048: NV 8 full, the widest
+LN_DIMS = [4, 100, 260, 768, 1024, 1280, 1300, 1600, 1796, 2048]
+LN_DIMS_BF16_DY = [100, 1024, 2048]  # the bf16-dy instantiations: NV 1 ragged, 4 and 8 full
 
 
 @pytest.mark.parametrize("D", LN_DIMS)
@@ -375,17 +392,31 @@ def test_layernorm_fwd_edges(T, D):
     assert_guards_intact(y, xs, h, xs_g, h_g)
 
 
-@pytest.mark.parametrize("pf", [1, 0])
-@pytest.mark.parametrize("D", LN_DIMS)
-@pytest.mark.parametrize("T", [1, 67])
-def test_layernorm_bwd_edges(T, D, pf):
+@contextlib.contextmanager
+def _ln_bwd_mode(pf, blocks=0):
+    """The LayerNorm backward with the row-prefetch kernel (1) or the one-row kernel (0), and
+    with ``blocks`` > 0 its persistent grid pinned to that many workgroups."""
+    lib = _lib.lib()
+    lib.dpc_layernorm_set_bwd_prefetch(pf)
+    lib.dpc_layernorm_set_bwd_blocks(blocks)
+    try:
+        yield
+    finally:
+        lib.dpc_layernorm_set_bwd_prefetch(-1)
+        lib.dpc_layernorm_set_bwd_blocks(0)
+
+
+def check_layernorm_bwd(T, D, pf, dy_bf16=False, blocks=0):
     """dx (accumulated and dx_set), dgamma, dbeta, and the fused consumer gout = bf16(dx * keep *
     relu'(gz)) with gsum; mean / rstd are the exact f64 statistics rounded to f32, as handed to
-    every implementation."""
+    every implementation.  ``dy_bf16``: the kernel is handed dy rounded to bf16 (the DYB
+    instantiations), and the reference and the ideal use the rounded values."""
     torch.manual_seed(17 * D + T)
     x = torch.randn(T, D, device=dev) + 3
     g = torch.randn(D, device=dev)
     dy = torch.randn(T, D, device=dev)
+    dy_k = dy.bfloat16() if dy_bf16 else dy  # what the kernel reads
+    dy = dy_k.float()
     dres = torch.randn(T, D, device=dev)
     _, mean64, rstd64 = _ln64(x, g, torch.zeros(D, device=dev))
     mean, rstd = mean64.float(), rstd64.float()
@@ -399,14 +430,11 @@ def test_layernorm_bwd_edges(T, D, pf):
     scratch = [guarded(D, F32, dev, fill=0.0) for _ in range(4)]
     gout = guarded((T, D), BF, dev, ld=_ld(D))
     gsum = guarded(D, F32, dev, fill=1.0)
-    _lib.lib().dpc_layernorm_set_bwd_prefetch(pf)
-    try:
-        layernorm_bwd(dy, x, mean, rstd, g, dx, dgam, dbet)
-        layernorm_bwd(dy, x, mean, rstd, g, dx_only, scratch[0], scratch[1], dx_set=True)
-        layernorm_bwd(dy, x, mean, rstd, g, dx2, scratch[2], scratch[3], gout=gout, gsum=gsum, drop=drop,
+    with _ln_bwd_mode(pf, blocks):
+        layernorm_bwd(dy_k, x, mean, rstd, g, dx, dgam, dbet)
+        layernorm_bwd(dy_k, x, mean, rstd, g, dx_only, scratch[0], scratch[1], dx_set=True)
+        layernorm_bwd(dy_k, x, mean, rstd, g, dx2, scratch[2], scratch[3], gout=gout, gsum=gsum, drop=drop,
                       gz=gz, gact=1)
-    finally:
-        _lib.lib().dpc_layernorm_set_bwd_prefetch(-1)
     m64, r64 = mean.double(), rstd.double()
     dx64, dg64, db64 = _ln_bwd(dy.double(), x.double(), m64, r64, g.double(), dres.double())
     dx32 = _ln_bwd(dy, x, mean, rstd, g, dres)[0]
@@ -419,9 +447,10 @@ def test_layernorm_bwd_edges(T, D, pf):
                        _ln_bwd(dy, x, mean, rstd, g, zero)[0], MARGIN, axes="rows", what="dx_set", family=fam + " dx")
     assert_elem_close(dgam, 0.5 + dg64, _sum_orders(dy * xh32, 0.5), MARGIN, what="dgamma", family=fam + " dgamma")
     assert_elem_close(dbet, -0.5 + db64, _sum_orders(dy, -0.5), MARGIN, what="dbeta", family=fam + " dbeta")
+    dg_orders, db_orders = _sum_orders(dy * xh32, 0.0), _sum_orders(dy, 0.0)
     for k in (0, 2):
-        assert_elem_close(scratch[k], dg64, _sum_orders(dy * xh32, 0.0), MARGIN, what="dgamma", family=fam + " dgamma")
-        assert_elem_close(scratch[k + 1], db64, _sum_orders(dy, 0.0), MARGIN, what="dbeta", family=fam + " dbeta")
+        assert_elem_close(scratch[k], dg64, dg_orders, MARGIN, what="dgamma", family=fam + " dgamma")
+        assert_elem_close(scratch[k + 1], db64, db_orders, MARGIN, what="dbeta", family=fam + " dbeta")
     mask64 = keep.double() * dact64(gz, 1)
     go64 = dx64 * mask64
     go32 = dx32 * keep * (gz.float() > 0).float()
@@ -432,33 +461,96 @@ def test_layernorm_bwd_edges(T, D, pf):
     dx3 = guarded((T, D), F32, dev, ld=_ld(D), fill=dres)
     gout_g, gsum_g = guarded((T, D), BF, dev, ld=_ld(D)), guarded(D, F32, dev, fill=1.0)
     extra = [guarded(D, F32, dev, fill=0.0) for _ in range(2)]
-    _lib.lib().dpc_layernorm_set_bwd_prefetch(pf)
-    try:
-        layernorm_bwd(dy, x, mean, rstd, g, dx3, extra[0], extra[1], gout=gout_g, gsum=gsum_g, drop=drop,
+    with _ln_bwd_mode(pf, blocks):
+        layernorm_bwd(dy_k, x, mean, rstd, g, dx3, extra[0], extra[1], gout=gout_g, gsum=gsum_g, drop=drop,
                       gz=gz, gact=2)
-    finally:
-        _lib.lib().dpc_layernorm_set_bwd_prefetch(-1)
     gg64 = dx64 * keep.double() * dgelu64(gz)
     gg32 = (dx32.double() * keep.double() * dgelu64(gz)).float()  # (f32 dx, GELU' exact, one rounding)
     assert_local_close(gout_g, gg64, gg32.bfloat16(), MARGIN, axes="rows", what="gout GELU'", family=fam + " gout")
     assert_guards_intact(dx, dx_only, dx2, dgam, dbet, *scratch, gout, gsum, dx3, gout_g, gsum_g, *extra)
 
 
+# (ids: the f32-dy cases keep the names they had before dy_bf16 was a parameter)
+LN_BWD_CASES = ([pytest.param(T, D, pf, False, id=f"{T}-{D}-{pf}") for pf in (1, 0) for D in LN_DIMS for T in (1, 67)]
+                + [pytest.param(T, D, pf, True, id=f"{T}-{D}-{pf}-dy_bf16")
+                   for pf in (1, 0) for D in LN_DIMS_BF16_DY for T in (1, 67)])
+
+
+@pytest.mark.parametrize("T,D,pf,dy_bf16", LN_BWD_CASES)
+def test_layernorm_bwd_edges(T, D, pf, dy_bf16):
+    """check_layernorm_bwd at one row and at 67 (a ragged last workgroup), both kernels, f32 dy
+    at every width class and bf16 dy at three of them."""
+    check_layernorm_bwd(T, D, pf, dy_bf16)
+
+
+def test_layernorm_refuses_wide_rows():
+    """D = 2052 is past the widest instantiation (8 vectors per lane): both directions raise."""
+    T, D = 3, 2052
+    x = torch.randn(T, D, device=dev)
+    g, b = torch.randn(D, device=dev), torch.randn(D, device=dev)
+    with pytest.raises(ValueError, match="D <= 2048"):
+        layernorm_fwd(x, g, b)
+    dx = guarded((T, D), F32, dev, fill=0.0)
+    dgam, dbet = guarded(D, F32, dev, fill=0.0), guarded(D, F32, dev, fill=0.0)
+    stat = torch.ones(T, device=dev)
+    with pytest.raises(ValueError, match="D <= 2048"):
+        layernorm_bwd(x, x, stat, stat, g, dx, dgam, dbet)
+    assert torch.count_nonzero(dx) == 0 and torch.count_nonzero(dgam) == 0 and torch.count_nonzero(dbet) == 0
+    assert_guards_intact(dx, dgam, dbet)
+
+
 # ---------------------------------------------------------------- cross-entropy
-@pytest.mark.parametrize("V,mode", [(1000, 0), (50257, 0), (50257, 1), (50257, 2), (50257, 3), (70001, 0)])
-@pytest.mark.parametrize("T", [1, 37])
-def test_cross_entropy_edges(T, V, mode):
-    """Per-row loss and gradient rows (the default dispatch, the three forced modes at V = 50257
-    -- 3 is the older register-resident ce_kernel<13> -- and the streaming fallback at V = 70001),
-    in place in a guarded [T, ld] buffer."""
-    torch.manual_seed(V + T)
-    ld = (V + 63) // 64 * 64
-    vals = (torch.randn(T, V, device=dev) * 2).bfloat16()
-    buf = guarded((T, ld), BF, dev, fill=0.0)
-    buf[:, :V] = vals
+# V -> ld = ceil64(V) -> 16-B chunks per thread of 512 (misc.hip: dpc_cross_entropy).  Mode 0:
+# 1000 ce_kernel2<1>; 4104 <2> nearly empty (ld 4160, one chunk past 4096); 8192 <2> full; 8200 <4>
+# just past <2>; 32768 <8> full; 50257 <13> (GPT-2); 53250 <16> ragged (ld 53312 > 13 x 4096);
+# 65536 <16> full, the last register-resident width; 65537 and 70001 the streaming kernel.
+CE_CASES = ([(1000, 0), (50257, 0), (50257, 1), (50257, 2), (50257, 3), (70001, 0)]
+            + [(V, 0) for V in (4104, 8192, 8200, 32768, 53250, 65536, 65537)])
+
+
+def _ce_targets(T, V):
+    """Random targets with every 7th row ignored; at T = 37 also the targets a kernel can get
+    wrong by position -- 0, V - 1, the first index of the tail chunk (V & 7) or of the last
+    chunk, one inside the last full chunk, and 8 * 512 * k (the first chunk of a thread's k-th
+    register) -- and rows 8 / 9 for the planted ties (their targets are set with the ties)."""
     tg = torch.randint(0, V, (T,), device=dev)
     if T > 1:
         tg[::7] = -100
+    if T >= 37:
+        last_full = V // 8 * 8 - (8 if V % 8 == 0 else 0)  # start of the last chunk / the tail chunk
+        k = (V - 1) // 4096
+        fixed = [0, V - 1, last_full, last_full - 3, 4096 * k, 4096 * max(k // 2, 0)]
+        for row, t in zip((1, 2, 3, 4, 5, 6), fixed):
+            tg[row] = t
+    return tg
+
+
+@pytest.mark.parametrize("V,mode", CE_CASES)
+@pytest.mark.parametrize("T", [1, 37])
+def test_cross_entropy_edges(T, V, mode):
+    """Per-row loss and gradient rows (the default dispatch at every register-resident width and
+    at the first streamed one, the three forced modes at V = 50257 -- 3 is the older
+    register-resident ce_kernel<13> -- and the streaming fallback at V = 70001), in place in a
+    guarded [T, ld] buffer.  At T = 37 rows 8 and 9 hold the row maximum twice, in different
+    chunks (the maximum copied to a column half a row away): the target on the first is a hit,
+    the target on the last is not.
+
+    [37-53250-0]: row 9's target is the row maximum, so its loss is log(s) = 5.012 alone.  With an
+    f32 log the kernel returned the float below the correctly rounded one there, 1.33 ulp from
+    the f64 value and 2.08 x the floor, although its s is within 4e-8; the kernels now take the
+    log in f64 (misc.hip: ce_kernel2)."""
+    torch.manual_seed(V + T)
+    ld = (V + 63) // 64 * 64
+    vals = (torch.randn(T, V, device=dev) * 2).bfloat16()
+    tg = _ce_targets(T, V)
+    if T >= 37:
+        for r in (8, 9):  # the row's maximum a second time, half a row away from the first
+            top = vals[r].max()
+            vals[r, (int(first_argmax(vals[r:r + 1])) + V // 2 + 5) % V] = top
+            at = (vals[r] == top).nonzero().flatten()
+            tg[r] = at[0] if r == 8 else at[-1]
+    buf = guarded((T, ld), BF, dev, fill=0.0)
+    buf[:, :V] = vals
     valid = tg != -100
     inv = (1.0 / valid.sum().clamp_min(1).float()).reshape(1)
     row_loss = guarded(T, F32, dev)
@@ -468,25 +560,9 @@ def test_cross_entropy_edges(T, V, mode):
         cross_entropy_rows(buf, tg, V, inv, row_loss, row_correct)
     finally:
         _lib.lib().dpc_ce_set_mode(-1)
-    safe = torch.where(valid, tg, torch.zeros_like(tg))
-    rows = torch.arange(T, device=dev)
-
-    def ce(lv):
-        lsm = torch.log_softmax(lv, -1)
-        loss = torch.where(valid, -lsm[rows, safe], torch.zeros_like(lsm[:, 0]))
-        p = torch.exp(lsm)
-        p[rows, safe] -= 1.0
-        return loss, p * (valid.to(lv.dtype) * inv.to(lv.dtype))[:, None]
-
-    loss64, grad64 = ce(vals.double())
-    loss32, grad32 = ce(vals.float())
-    assert_local_close(row_loss, loss64, loss32, MARGIN, axes="cols", what="row loss", family="cross-entropy loss")
-    assert_local_close(buf[:, :V], grad64, grad32.bfloat16(), MARGIN, axes="rows", what="dlogits",
-                       family="cross-entropy grad")
-    assert torch.count_nonzero(buf[~valid]) == 0        # ignored rows: exactly zero
-    assert torch.count_nonzero(buf[:, V:]) == 0         # padded columns: exactly zero
-    hit = ((vals.float().argmax(-1) == tg) & valid).float()
-    assert torch.equal(row_correct, hit)
+    check_cross_entropy(row_loss, buf[:, :V], buf[:, V:], row_correct, vals, tg, inv)
+    if T >= 37:
+        assert row_correct[8] == 1.0 and row_correct[9] == 0.0
     assert_guards_intact(buf, row_loss, row_correct)
 
 
@@ -636,12 +712,20 @@ def test_cast_edges(n):
     assert_guards_intact(dst)
 
 
-@pytest.mark.parametrize("M", [1, 16])
-@pytest.mark.parametrize("epi", ["plain", "bias_gelu", "bias_relu_res"])
-def test_linear_few_rows_edges(M, epi):
+# M = 1, 2, 9, 16 launch gemv_kernel<1>, <2>, <16> with 7 masked rows, <16> full (<4> and <8>:
+# test_kernels_gpu.py).  K = 64: one trip of the K loop that lanes 0..7 enter; K = 520: a second
+# trip (k = 512) that only lane 0 enters.  (ids: the K = 64 cases keep the names they had.)
+FEW_ROWS_CASES = ([pytest.param(epi, M, 64, id=f"{epi}-{M}") for M in (1, 16, 2, 9)
+                   for epi in ("plain", "bias_gelu", "bias_relu_res")]
+                  + [pytest.param(epi, M, 520, id=f"{epi}-{M}-K520") for M in (1, 16, 2, 9)
+                     for epi in ("plain", "bias_gelu", "bias_relu_res")])
+
+
+@pytest.mark.parametrize("epi,M,K", FEW_ROWS_CASES)
+def test_linear_few_rows_edges(epi, M, K):
     """csrc/decode.hip dpc_gemv through linear_fwd(out=): Nw = 100 weight rows into N = 104 output
-    columns (the padding written as 0), K = 64."""
-    Nw, N, K = 100, 104, 64
+    columns (the padding written as 0), K = 64 or 520."""
+    Nw, N = 100, 104
     torch.manual_seed(7 + M)
     x = torch.randn(M, K, device=dev).bfloat16()
     w = (torch.randn(Nw, K, device=dev) / K ** 0.5).bfloat16()

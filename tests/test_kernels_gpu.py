@@ -703,8 +703,9 @@ def test_embedding_bwd_deterministic(D):
 @pytest.mark.parametrize("V,mode", [(50257, 0), (1000, 0), (9000, 0), (40000, 0), (70001, 0),
                                     (50257, 1), (50257, 2)])
 def test_cross_entropy(V, mode):
-    """Register-resident rows (ce_kernel<1..16>: V = 1000 .. 50257), the streaming fallback
-    (V = 70001 > 64K columns) and the forced streaming modes, all in place."""
+    """Register-resident rows -- ce_kernel2<1> (V = 1000), <4> (9000) and <13> (40000, 50257) --
+    the streaming fallback ce_stream_kernel<4> (V = 70001 > 64K columns) and the forced streaming
+    modes, all in place.  (ce_kernel2<2>, <8> and <16>: test_kernel_edges_gpu.py.)"""
     torch.manual_seed(6)
     T = 300
     ld = (V + 63) // 64 * 64
