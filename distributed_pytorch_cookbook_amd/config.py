@@ -50,6 +50,18 @@ def build_parser(recipe: str = "single") -> argparse.ArgumentParser:
                         "parameter moves, so the optimizer runs after every gradient collective has finished: "
                         "the bucket-by-bucket (DDP, PP x DP) and unit-by-unit (FSDP) AdamW overlap is not "
                         "available with clipping")
+    p.add_argument("--lr_schedule", type=str, default="constant", choices=["constant", "linear", "cosine"],
+                   help="learning-rate schedule after the warmup (ops/schedule.py, docs/LR_SCHEDULE.md): evaluated "
+                        "on the device inside the AdamW kernel from the applied-step counter, so it advances on "
+                        "every replay of the captured step; constant with --warmup_steps 0 = no schedule")
+    p.add_argument("--warmup_steps", type=int, default=0, help="linear warmup from --learning_rate / N over N steps")
+    p.add_argument("--lr_decay_steps", type=int, default=0,
+                   help="the step at which the linear / cosine decay reaches its floor (0 = the whole run)")
+    p.add_argument("--min_lr_ratio", type=float, default=0.1,
+                   help="floor of the linear / cosine decay as a fraction of --learning_rate")
+    p.add_argument("--weight_decay", type=float, default=0.01, help="AdamW decoupled weight decay")
+    p.add_argument("--adam_beta1", type=float, default=0.9)
+    p.add_argument("--adam_beta2", type=float, default=0.999)
     p.add_argument("--dropout", type=float, default=0.0)
     p.add_argument("--recompute", action="store_true",
                    help="activation recompute: keep only each layer's input, re-run its forward in backward")

@@ -6,6 +6,8 @@ observation 2); here that difference is an ``Engine`` and the loop is shared
 """
 from __future__ import annotations
 
+import gc
+
 import torch
 import torch.distributed as dist
 
@@ -50,6 +52,30 @@ class Engine:
         """Global gradient norm of the last step before clipping (a 0-dim device tensor; the same
         on every rank), or None without --max_grad_norm."""
         return None if self.clipper is None else self.clipper.norm_t
+
+    @staticmethod
+    def _opt_kwargs(weight_decay: float, betas, lr_schedule) -> dict:
+        """The optimizer hyperparameters an engine forwards to every FlatAdamW it builds."""
+        return {"weight_decay": weight_decay, "betas": tuple(betas), "lr_schedule": lr_schedule}
+
+    def set_lr_schedule(self, s) -> None:
+        """Install an ``ops.schedule.LRSchedule`` (None: remove it) on every optimizer of the
+        engine.  Before the step is captured: the schedule's parameters are kernel arguments,
+        baked into the HIP graph (its position is not -- the kernel reads the device counter)."""
+        stepper = getattr(self, "_stepper", None)
+        if stepper is not None and stepper.graph is not None:
+            raise RuntimeError("set_lr_schedule after the step was captured into a HIP graph: the "
+                               "schedule's parameters are baked into it; install it before training")
+        for o, _, _ in self.parts:
+            o.set_lr_schedule(s)
+
+    @property
+    def lr(self):
+        """The learning rate the last step used (a host float), or None without a schedule: the
+        schedule at the first optimizer's applied-step count.  Where that count lives on the
+        device (HIP-graph replay, loss scaler) reading it synchronises -- read it where the loop
+        already has, as ``grad_norm``."""
+        return self.parts[0][0].last_lr if self.parts else None
 
     def _scaled(self, loss):
         return self.scaler.scale(loss) if self.scaler is not None else loss
@@ -233,6 +259,11 @@ class GraphedStep:
         wd = self._watchdog()
         native_wd = wd.watchdog_running()
         err = None
+        # no cyclic garbage collection while the capture runs: a collection that starts inside it
+        # -- in this thread or in autograd's -- would run finalizers (tensors, events, an earlier
+        # engine's graph) in the middle of a "global"-mode capture
+        gc_on = gc.isenabled()
+        gc.disable()
         try:
             # thread_local: only this thread's calls are checked -- the process group's and
             # the native watchdog threads keep querying their events while the capture runs
@@ -245,6 +276,8 @@ class GraphedStep:
             err = exc
         finally:
             wd.watchdog_pause(False)
+            if gc_on:
+                gc.enable()
         if multi:
             # every rank graphs or none does: a rank replaying while another runs eagerly
             # would still issue the same collectives, but a failed capture may have left

@@ -27,7 +27,8 @@ class DataParallelEngine(Engine):
     def __init__(self, model, device, lr: float, group=None, bucket_mb: float = 128.0,
                  reduce_dtype=torch.float32, overlap: bool = True, compute_dtype=None,
                  graph: bool = False, comm_kind: str | None = None, grad_scaler: bool = False,
-                 force_ddp_store: bool = False, max_grad_norm: float = 0.0):
+                 force_ddp_store: bool = False, max_grad_norm: float = 0.0,
+                 weight_decay: float = 1e-2, betas=(0.9, 0.999), lr_schedule=None):
         self.device = torch.device(device)
         self.model = model
         self.dp_group = group
@@ -41,7 +42,8 @@ class DataParallelEngine(Engine):
                                   comm_kind=comm_kind)
         else:
             self.store = LocalStore(model, device, compute_dtype=compute_dtype)
-        self.opt = FlatAdamW(self.store.master, self.store.grads, lr=lr, shadow=self.store.shadow)
+        self.opt = FlatAdamW(self.store.master, self.store.grads, lr=lr, shadow=self.store.shadow,
+                             **self._opt_kwargs(weight_decay, betas, lr_schedule))
         self._make_scaler_clipper(grad_scaler, max_grad_norm)
         # all-reduced gradients are identical on every rank, so are the skip flag and the norm
         # (its sum has a fixed order: ops/clip.py) -- no collective for either

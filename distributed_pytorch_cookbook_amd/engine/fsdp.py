@@ -29,7 +29,8 @@ class FSDPEngine(Engine):
     def __init__(self, model, device, lr: float, group=None, prefetch: int = 1,
                  reshard_after_forward: bool = True, cpu_offload: bool = False, compute_dtype=None,
                  reduce_dtype=torch.float32, grad_scaler: bool = False, graph: bool = False,
-                 comm_kind: str | None = None, force_sharded: bool = False, max_grad_norm: float = 0.0):
+                 comm_kind: str | None = None, force_sharded: bool = False, max_grad_norm: float = 0.0,
+                 weight_decay: float = 1e-2, betas=(0.9, 0.999), lr_schedule=None):
         self.device = torch.device(device)
         self.model = model
         self.dp_group = group
@@ -42,8 +43,9 @@ class FSDPEngine(Engine):
                                force_sharded=force_sharded)
         st = self.store
         grad = st.grads_host if st.cpu_offload else st.grads
-        self.opt = FlatAdamW(st.master, grad, lr=lr, shadow=st.shadow)
-        self.opt_rep = FlatAdamW(st.rep_master, st.rep_grads, lr=lr)  # replicated 1-D params
+        okw = self._opt_kwargs(weight_decay, betas, lr_schedule)
+        self.opt = FlatAdamW(st.master, grad, lr=lr, shadow=st.shadow, **okw)
+        self.opt_rep = FlatAdamW(st.rep_master, st.rep_grads, lr=lr, **okw)  # replicated 1-D params
         self._make_scaler_clipper(grad_scaler, max_grad_norm)
         # The shards differ per rank: the skip flag and the shards' squared norm are reduced over
         # the group; the replicated 1-D gradients are all-reduced by finish_grads and counted
@@ -104,14 +106,17 @@ class FSDPEngine(Engine):
         st = self.store
         m = st.gather_full(self.opt.exp_avg, dst_rank=0, rep_flat=self.opt_rep.exp_avg)
         v = st.gather_full(self.opt.exp_avg_sq, dst_rank=0, rep_flat=self.opt_rep.exp_avg_sq)
+        s = self.opt.lr_schedule
         return {"optimizer": {"step": self.opt.step_count, "exp_avg": m, "exp_avg_sq": v,
-                              "format": "canonical"}, **self._scaler_state()}
+                              "format": "canonical", "applied_step": self.opt.applied_steps,
+                              "lr_schedule": s.params() if s is not None else None},
+                **self._scaler_state()}
 
     def load_train_state(self, st):
         self.store.wait_host()
         o = st["optimizer"]
-        self.opt.step_count = int(o["step"])
-        self.opt_rep.step_count = int(o["step"])
+        for opt in (self.opt, self.opt_rep):
+            opt.set_steps(o["step"], o.get("applied_step"))
         if isinstance(o.get("exp_avg"), dict):
             self.store.load_full(o["exp_avg"], self.opt.exp_avg, rep_flat=self.opt_rep.exp_avg)
             self.store.load_full(o["exp_avg_sq"], self.opt.exp_avg_sq, rep_flat=self.opt_rep.exp_avg_sq)

@@ -44,7 +44,8 @@ class PipelineEngine(Engine):
                  schedule: str = "1f1b", bucket_mb: float = 128.0, compute_dtype=None,
                  seq_len: int | None = None, grad_scaler: bool = False, comm_kind: str | None = None,
                  wire_dtype=None, graph: bool = False, force_dist: bool = False,
-                 reduce_dtype=torch.float32, max_grad_norm: float = 0.0):
+                 reduce_dtype=torch.float32, max_grad_norm: float = 0.0,
+                 weight_decay: float = 1e-2, betas=(0.9, 0.999), lr_schedule=None):
         self.device = torch.device(device)
         self.model = model
         self._make_scaler_clipper(grad_scaler, max_grad_norm)
@@ -99,7 +100,8 @@ class PipelineEngine(Engine):
         else:
             self.store = LocalStore(model, device, compute_dtype=compute_dtype, units=self.my_units)
         self.store.accum_steps = self.n_micro
-        self.opt = FlatAdamW(self.store.master, self.store.grads, lr=lr, shadow=self.store.shadow)
+        self.opt = FlatAdamW(self.store.master, self.store.grads, lr=lr, shadow=self.store.shadow,
+                             **self._opt_kwargs(weight_decay, betas, lr_schedule))
         # Every stage holds different gradients: one skip decision for the whole job.  The stages
         # hold disjoint units (no weight is tied across stages), so the global norm sums the
         # stages' squares over the pipeline group; with PP x DP the replica all-reduce has already
@@ -315,12 +317,15 @@ class PipelineEngine(Engine):
     def train_state(self):
         m = self._gather_named(self._named_flat(self.opt.exp_avg))
         v = self._gather_named(self._named_flat(self.opt.exp_avg_sq))
+        s = self.opt.lr_schedule
         return {"optimizer": {"step": self.opt.step_count, "exp_avg": m, "exp_avg_sq": v,
-                              "format": "canonical"}, **self._scaler_state()}
+                              "format": "canonical", "applied_step": self.opt.applied_steps,
+                              "lr_schedule": s.params() if s is not None else None},
+                **self._scaler_state()}
 
     def load_train_state(self, st):
         o = st["optimizer"]
-        self.opt.step_count = int(o["step"])
+        self.opt.set_steps(o["step"], o.get("applied_step"))
         for key, flat in (("exp_avg", self.opt.exp_avg), ("exp_avg_sq", self.opt.exp_avg_sq)):
             d = o.get(key)
             if isinstance(d, dict):

@@ -106,6 +106,9 @@ class Trainer:
         self.start_epoch = 0
         self.skip_batches = 0  # batches of start_epoch already trained (mid-epoch resume)
         self.history = []
+        self.lr_schedule = None      # ops.schedule.LRSchedule installed by fit (None: constant rate)
+        self.resumed = False          # maybe_resume restored a training state
+        self.resumed_schedule = None  # the schedule parameters that state recorded
         vocab = getattr(tokenizer, "vocab_size", 50257)
         self.flops_per_token = train_flops_per_token(args.dim, args.heads, args.head_dim, args.num_layers,
                                                      vocab, args.sequence_length)
@@ -128,6 +131,10 @@ class Trainer:
         st = load_train_state(path)
         if st is not None:
             self.engine.load_train_state(st)
+            # (the schedule's position is the count of applied updates just restored; its shape
+            # comes from this run's flags -- _install_lr_schedule notes a difference once T is resolved)
+            self.resumed = True
+            self.resumed_schedule = (st.get("optimizer") or {}).get("lr_schedule")
             self.start_epoch = int(st.get("epoch", 0))
             self.skip_batches = int(st.get("batch", 0))
             rng = st.get("rng_per_rank")
@@ -137,6 +144,30 @@ class Trainer:
                 set_rng_state(st["rng"])
         if self.log:
             print(f"[resume] loaded {path} (epoch {self.start_epoch}, batch {self.skip_batches})")
+
+    def _install_lr_schedule(self, steps_per_epoch: int) -> None:
+        """--lr_schedule / --warmup_steps: build the schedule now that the length of the run is
+        known and install it on every optimizer of the engine, before the first step (its
+        parameters are baked into the captured step).  Constant without warmup installs nothing."""
+        a = self.args
+        kind = getattr(a, "lr_schedule", "constant")
+        W = int(getattr(a, "warmup_steps", 0) or 0)
+        sched = None
+        if kind != "constant" or W > 0:
+            from ..ops.schedule import LRSchedule
+
+            T = int(getattr(a, "lr_decay_steps", 0) or 0) or a.epochs * steps_per_epoch
+            sched = LRSchedule(kind, a.learning_rate, W, T, getattr(a, "min_lr_ratio", 0.1))
+            self.engine.set_lr_schedule(sched)
+            if self.log:
+                print(f"[lr_schedule] {kind}: warmup W={W}, decay ends at T={T}, "
+                      f"peak L={sched.base_lr:g}, floor m={sched.min_lr:g}")
+        self.lr_schedule = sched
+        now = None if sched is None else sched.params()
+        if self.log and self.resumed and self.resumed_schedule != now and (
+                self.resumed_schedule is not None or now is not None):
+            print(f"[resume] the checkpoint was written with lr schedule {self.resumed_schedule}, "
+                  f"this run's flags give {now}: the flags win (the position is the optimizer step)")
 
     # ------------------------------------------------------------------ main loop
     def fit(self, train_ds, val_ds):
@@ -180,6 +211,8 @@ class Trainer:
                                                 True, a.seed, self.device)
             val_loader, _ = make_loader(val_ds, a.batch_size, min(a.num_workers, 2), e.dp_world, e.dp_rank,
                                         False, a.seed, self.device)
+        per_epoch = len(train_loader)  # (--data_path: the trainer's own ``steps``)
+        self._install_lr_schedule(min(per_epoch, a.max_steps) if a.max_steps else per_epoch)
         for ei in range(self.start_epoch, a.epochs):
             if sampler is not None:
                 # the shuffle order is a function of (seed, epoch) alone, so a resumed run sees
@@ -243,6 +276,9 @@ class Trainer:
                     # --max_grad_norm: the last step's norm before clipping (read here, where the
                     # loop has just synchronised)
                     rec["grad_norm"] = float(e.grad_norm)
+                lr = e.lr  # the rate the last step used (a device step counter is read here too)
+                if lr is not None:
+                    rec["lr"] = lr
                 self.history.append(rec)
                 self._jsonl(rec)
                 window, nwin, tokens, t0 = None, 0, 0, time.perf_counter()

@@ -130,6 +130,9 @@ class AdamArgs(ctypes.Structure):
         ("weight_decay", c_float), ("bias_correction1", c_float),
         ("bias_correction2_sqrt", c_float), ("grad_scale", c_float),
         ("step_ptr", P), ("skip_ptr", P),
+        # learning-rate schedule (ops/schedule.py): kind 0 = none, lr is used as passed
+        ("sched_kind", c_int), ("sched_warmup", c_float), ("sched_decay", c_float),
+        ("sched_min_lr", c_float), ("sched_t", c_float),
     ]
 
 

@@ -167,7 +167,7 @@ class FSDPStore(ParamStore):
         b1, b2 = opt.betas
         hs = self._hshadow[sl] if self._hshadow is not None else None
         runtime.adamw_host(self.master[sl], self.grads_host[sl], opt.exp_avg[sl], opt.exp_avg_sq[sl],
-                           opt.lr, b1, b2, opt.eps, opt.weight_decay, step, grad_scale, hs)
+                           opt.rate(step), b1, b2, opt.eps, opt.weight_decay, step, grad_scale, hs)
         with torch.cuda.device(self.device), torch.cuda.stream(self._copy):
             self.shadow[sl].copy_(hs if hs is not None else self.master[sl], non_blocking=True)
             up = torch.cuda.Event()

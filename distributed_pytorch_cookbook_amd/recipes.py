@@ -67,6 +67,10 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
     graph = (not args.disable_compile and not args.disable_amp
              and not getattr(args, "coll_check", False))
     max_grad_norm = float(getattr(args, "max_grad_norm", 0.0) or 0.0)
+    # AdamW hyperparameters of every optimizer the engine builds (the learning-rate schedule is
+    # installed by the trainer once the length of the run is known: Trainer.fit)
+    optim = {"weight_decay": float(getattr(args, "weight_decay", 1e-2)),
+             "betas": (float(getattr(args, "adam_beta1", 0.9)), float(getattr(args, "adam_beta2", 0.999)))}
     if recipe in ("single", "ddp"):
         from .engine.data_parallel import DataParallelEngine
 
@@ -75,7 +79,7 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
             reduce_dtype=reduce_dtype,
             overlap=not args.no_overlap, compute_dtype=compute_dtype, graph=graph,
             comm_kind=comm_kind, grad_scaler=getattr(args, "grad_scaler", False), force_ddp_store=force_dist,
-            max_grad_norm=max_grad_norm,
+            max_grad_norm=max_grad_norm, **optim,
         )
     if recipe == "fsdp":
         from .engine.fsdp import FSDPEngine
@@ -84,7 +88,7 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
                           reshard_after_forward=not args.no_reshard_after_forward,
                           cpu_offload=args.cpu_offload, compute_dtype=compute_dtype,
                           reduce_dtype=reduce_dtype, grad_scaler=getattr(args, "grad_scaler", False), graph=graph, comm_kind=comm_kind,
-                          force_sharded=force_dist, max_grad_norm=max_grad_norm)
+                          force_sharded=force_dist, max_grad_norm=max_grad_norm, **optim)
     if recipe in ("pipe", "pipe_ddp"):
         from .engine.pipeline import PipelineEngine
 
@@ -95,7 +99,7 @@ def build_engine(recipe: str, model, info, args, force_dist: bool = False):
                               schedule=args.schedule, bucket_mb=args.bucket_mb,
                               compute_dtype=compute_dtype, grad_scaler=getattr(args, "grad_scaler", False),
                               comm_kind=comm_kind, wire_dtype=wire, graph=graph, force_dist=force_dist,
-                              reduce_dtype=reduce_dtype, max_grad_norm=max_grad_norm)
+                              reduce_dtype=reduce_dtype, max_grad_norm=max_grad_norm, **optim)
     raise ValueError(recipe)
 
 

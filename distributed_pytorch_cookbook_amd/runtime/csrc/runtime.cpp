@@ -246,7 +246,10 @@ API void dpc_adamw_host(float* p, const float* g, float* m, float* v, int64_t n,
 #pragma omp parallel for simd schedule(static)
   for (int64_t i = 0; i < n; ++i) {
     const float gi = g[i] * grad_scale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    // first moment with the rounding error of (1 - b1) g carried along: where 0.9 m and 0.1 g
+    // cancel, the sum would otherwise keep the absolute error of its terms
+    const float t0 = (1.f - b1) * gi;
+    const float mi = std::fma(b1, m[i], t0) + std::fma(1.f - b1, gi, -t0);
     const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
     m[i] = mi;
     v[i] = vi;
