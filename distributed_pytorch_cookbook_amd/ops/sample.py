@@ -8,8 +8,8 @@ them, so "sort and cut" is not well defined):
 * top-p (``p < 1``): softmax ``q`` over the top-k survivors; keep ``i`` iff the mass of the kept
   values strictly greater than ``z_i`` is ``< p``.  The largest value always stays.
 * draw: ``w_i = exp(z_i - max)`` over the kept set, ``Z = sum w``; the token is the first kept
-  index, in index order, whose inclusive prefix sum exceeds ``u Z`` (the last kept index if
-  rounding leaves none).
+  index, in index order, whose inclusive prefix sum exceeds ``u Z`` (if none does -- ``u = 1``, or
+  rounding -- the last kept index of positive weight: a kept ``-inf`` is never drawn).
 * ``u`` is counter-based: ``sample_uniform(seed, row, counters[row])``, 24 bits of an ``fmix32``
   chain (``csrc/common.h``; the torch twin of the hash is in ``ops/dropout.py``).  The counters
   live on the device and every call advances them, so a replayed HIP graph draws a fresh number
@@ -75,7 +75,7 @@ def sample_reference(logits: torch.Tensor, temperature: float, top_k: int, top_p
     hit = kept & (cum > u.to(dtype).reshape(-1, 1) * cum[:, -1:])
     V = logits.shape[1]
     idx = torch.arange(V, device=logits.device)
-    last = torch.where(kept, idx, torch.zeros_like(idx)).amax(-1)
+    last = torch.where(w > 0, idx, torch.zeros_like(idx)).amax(-1)  # (the maximum's weight is 1)
     return torch.where(hit.any(-1), torch.argmax(hit.to(torch.uint8), dim=-1), last)
 
 

@@ -5,13 +5,15 @@ import math
 import pytest
 import torch
 
+import sample_cases as sc
 from kernel_checks import MARGIN_ATTN, assert_guards_intact, assert_local_close, guarded
+from sample_cases import CONFIGS, ROWS, config_rows
 
 from distributed_pytorch_cookbook_amd.models.fused import vocab_ld
 from distributed_pytorch_cookbook_amd.models.gpt import TransformerDecoderLM
 from distributed_pytorch_cookbook_amd.ops import _lib
 from distributed_pytorch_cookbook_amd.ops.attention import decode_attention
-from distributed_pytorch_cookbook_amd.ops.sample import sample_logits, sample_uniform
+from distributed_pytorch_cookbook_amd.ops.sample import MAX_VOCAB, sample_logits, sample_uniform
 from distributed_pytorch_cookbook_amd.utils.batch import generate_batch
 from distributed_pytorch_cookbook_amd.utils.tokenizer import ByteTokenizer
 
@@ -19,20 +21,7 @@ pytestmark = pytest.mark.gpu
 dev = "cuda"
 BF, F32 = torch.bfloat16, torch.float32
 
-ROWS = 64
-CONFIGS = [(3.0, 50257), (1.0, 50257), (6.0, 1000)]
 TEMPERATURE, TOP_K, TOP_P = 0.8, 50, 0.9
-_rows_cache = {}
-
-
-def config_rows(i):
-    """The 64 rows of configuration i, drawn row after row from one CPU stream over the three
-    configurations in order (made once, never modified)."""
-    if not _rows_cache:
-        torch.manual_seed(0)
-        for c, (scale, V) in enumerate(CONFIGS):
-            _rows_cache[c] = torch.stack([(torch.randn(V) * scale).bfloat16() for _ in range(ROWS)])
-    return _rows_cache[i]
 
 
 def strided(rows):
@@ -52,46 +41,167 @@ def draw(logits, counters=None, **kw):
     return out[:, 0].cpu()
 
 
-def oracle_row(row, temperature, top_k, top_p):
-    """The definition in f64 for one row: (kept, w, ambiguous) -- the kept mask, exp(z - max), and
-    the top-k survivors whose strictly-greater mass lies within 1e-4 of top_p."""
-    z = row.double() / temperature
-    vals, inv, counts = torch.unique(z, return_inverse=True, return_counts=True)  # ascending
-    count_gt = counts.sum() - torch.cumsum(counts, 0)
-    keep_k = count_gt[inv] < top_k if top_k > 0 else torch.ones_like(z, dtype=torch.bool)
-    w = torch.exp(z - z.max())
-    mass = torch.zeros_like(vals).index_add_(0, inv, w * keep_k)
-    q_gt = ((mass.sum() - torch.cumsum(mass, 0)) / mass.sum())[inv]
-    kept = keep_k & ((q_gt < top_p) | (z == z.max()))
-    ambiguous = keep_k & ((q_gt - top_p).abs() <= 1e-4)
-    return kept, w, ambiguous
-
-
 @pytest.mark.parametrize("ci", range(len(CONFIGS)))
 def test_sampler_exact_draw_against_f64(ci):
     rows = config_rows(ci)
-    V = rows.shape[1]
     u = torch.tensor([sample_uniform(1234, r, 7) for r in range(ROWS)], dtype=F32)
     tok = draw(strided(rows), temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, u=u.to(dev)).tolist()
-    assert all(0 <= t < V for t in tok), "a padding column was drawn"
+    assert all(0 <= t < rows.shape[1] for t in tok), "a padding column was drawn"
     # the same rows packed tight (an odd row stride at V = 50257: rows off the 16-B boundary)
     assert draw(rows.to(dev), temperature=TEMPERATURE, top_k=TOP_K, top_p=TOP_P, u=u.to(dev)).tolist() == tok
-    n_ambiguous, largest = 0, 0
-    for r in range(ROWS):
-        kept, w, amb = oracle_row(rows[r], TEMPERATURE, TOP_K, TOP_P)
-        largest = max(largest, int(kept.sum()))
-        t = tok[r]
-        if amb.any():
-            n_ambiguous += 1
-            assert kept[t] or amb[t], (r, t)
-            continue
-        assert kept[t], (r, t)
-        cum = torch.cumsum(w * kept, 0)
-        Z = cum[-1].item()
-        lo, hi = (cum[t] - w[t]).item() - 1e-5 * Z, cum[t].item() + 1e-5 * Z
-        assert lo <= u[r].double().item() * Z <= hi, (r, t, lo / Z, u[r].item(), hi / Z)
+    n_ambiguous, largest = sc.check_interval_rows(rows, u, tok, TEMPERATURE, TOP_K, TOP_P, what=str(CONFIGS[ci]))
     print(f"config {CONFIGS[ci]}: {n_ambiguous} ambiguous rows, kept sets up to {largest}")
     assert n_ambiguous <= 4
+
+
+@pytest.mark.parametrize("ci,setting", sc.MATRIX, ids=str)
+def test_sampler_random_row_matrix(ci, setting):
+    """The exact-draw check over the parameters: each cut alone, top_k on both sides of the
+    shortcut's limit and past V, both cuts, a cold and a hot temperature."""
+    rows = config_rows(ci)
+    temperature, top_k, top_p = setting
+    u = torch.tensor([sample_uniform(1234, r, 7) for r in range(ROWS)], dtype=F32)
+    kw = dict(temperature=temperature, top_k=top_k, top_p=top_p, u=u.to(dev))
+    tok = draw(strided(rows), **kw).tolist()
+    assert draw(rows.to(dev), **kw).tolist() == tok
+    n_ambiguous, largest = sc.check_interval_rows(rows, u, tok, *setting, what=f"{CONFIGS[ci]} {setting}")
+    print(f"config {CONFIGS[ci]} {setting}: {n_ambiguous} ambiguous rows, kept sets up to {largest}")
+
+
+# ---------------------------------------------------------------- constructed cases: no row excused
+def run_case(c, tight):
+    rows = c.row.to(dev).expand(len(c.u), c.V)
+    logits = rows.contiguous() if tight else strided(rows)
+    return draw(logits, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p, u=c.u.to(dev))
+
+
+def check_cases(cases, what):
+    """Every case in a ``vocab_ld`` buffer with +1e4 in the padding and packed tight (rows on and
+    off the 16-B boundary): the same tokens, and the f64 oracle's."""
+    n_rows = excused = 0
+    for c in cases:
+        tok = run_case(c, tight=False)
+        excused += sc.check_tokens(c, tok)
+        assert torch.equal(run_case(c, tight=True), tok), f"{c.name}: the packed rows draw other tokens"
+        n_rows += len(tok)
+    print(f"{what}: {len(cases)} cases, {n_rows} rows in each layout, {excused} rows excused")
+    assert excused == 0
+
+
+@pytest.mark.parametrize("V", sc.LATTICE_VOCABS)
+def test_sampler_lattice_cases(V):
+    """Rows of a dozen tied levels: each cut alone and both, top_k just below and just inside every
+    level, top_p midway between the cumulative masses, with the threshold key in every position
+    of the two histogram passes (tests/sample_cases.py)."""
+    check_cases(sc.lattice_cases(V), f"lattice V = {V}")
+
+
+@pytest.mark.parametrize("V", sc.WALK_VOCABS)
+def test_sampler_walk_cases(V):
+    """Draws aimed at every edge of the walk (row ends, wave segments, iterations, lanes,
+    elements), over a dense and a sparse kept set, and u = 0 / u = 1 over -inf ends."""
+    check_cases(sc.walk_cases(V), f"walk V = {V}")
+
+
+@pytest.mark.parametrize("V", sc.WIDTH_VOCABS)
+def test_sampler_width_cases(V):
+    check_cases(sc.width_cases(V), f"width V = {V}")
+
+
+# ---------------------------------------------------------------- invariants, bit for bit
+@pytest.mark.parametrize("V", sc.LATTICE_VOCABS)
+def test_sampler_top_k_past_the_vocabulary_is_off(V):
+    """top_k = 0, V and V + 7 draw the same tokens (the hash path: every row its own uniform)."""
+    logits = strided(sc.lattice_row(V).expand(ROWS, V))
+    for top_p in (1.0, 0.7):
+        toks = [draw(logits, temperature=sc.LATTICE_T, top_k=k, top_p=top_p, seed=21) for k in (0, V, V + 7)]
+        assert torch.equal(toks[0], toks[1]) and torch.equal(toks[0], toks[2]), top_p
+        assert len(set(toks[0].tolist())) > ROWS // 2  # (the rows draw different uniforms)
+
+
+@pytest.mark.parametrize("ci", [0, 2])
+def test_sampler_top_k_past_the_vocabulary_is_off_random_rows(ci):
+    logits = strided(config_rows(ci))
+    V = logits.shape[1]
+    toks = [draw(logits, temperature=1.5, top_k=k, top_p=0.95, seed=22) for k in (0, V, V + 7)]
+    assert torch.equal(toks[0], toks[1]) and torch.equal(toks[0], toks[2])
+
+
+@pytest.mark.parametrize("V", sc.LATTICE_VOCABS)
+def test_sampler_hash_path_is_the_explicit_uniform(V):
+    """One case of each instantiation: the hash of (seed, row, counter) on the device draws what
+    the host twin's uniform draws when it is passed in."""
+    logits = strided(sc.lattice_row(V).expand(ROWS, V))
+    seed = (0x1234 << 32) | 77
+    kw = dict(temperature=sc.LATTICE_T, top_k=2525, top_p=0.9)
+    counters = torch.full((ROWS,), 3, dtype=torch.int64, device=dev)
+    by_hash = draw(logits, counters, seed=seed, **kw)
+    assert counters.tolist() == [4] * ROWS
+    u = torch.tensor([sample_uniform(seed, r, 3) for r in range(ROWS)], dtype=F32, device=dev)
+    assert torch.equal(draw(logits, u=u, **kw), by_hash)
+    assert len(set(by_hash.tolist())) > ROWS // 2
+
+
+def test_sampler_distribution_chi2_wide_kernel():
+    """8192 hash draws from one V = 8200 vector (sample_kernel<7>) at top_k = 5: Pearson's
+    chi-squared against the f64 probabilities below 33.4, the 1 - 1e-6 quantile at 4 degrees of
+    freedom.  8200 columns span the segments of waves 0, 1 and 2 only (3584 columns each): the
+    five survivors lie in all three, in five different (wave, iteration) registers."""
+    V, n = 8200, 8192
+    cols = [5, 3000, 4613, 7167, 8199]
+    where = [sc.walk_position(c, V)[:2] for c in cols]
+    assert where == [(0, 0), (0, 5), (1, 2), (1, 6), (2, 2)]
+    vec = torch.tensor([-0.5, -1.0, -3.0, -1.5]).repeat(V // 4).bfloat16()
+    vec[cols] = torch.tensor([1.5, 0.0, 2.0, 0.5, 1.0]).bfloat16()
+    p = torch.zeros(V, dtype=torch.float64)
+    p[cols] = torch.softmax(vec.double()[cols], 0)
+    tok = draw(vec.to(dev).repeat(n, 1), temperature=1.0, top_k=5, seed=5)
+    counts = torch.bincount(tok, minlength=V).double()
+    assert counts[cols].sum() == n == counts.sum()
+    chi2 = (((counts - n * p) ** 2)[cols] / (n * p[cols])).sum().item()
+    print(f"chi2 = {chi2:.2f}")
+    assert chi2 < 33.4
+
+
+# ---------------------------------------------------------------- refusals
+def test_sampler_refuses_bad_shapes():
+    """A row past MAX_VOCAB raises in the wrapper; the native entry refuses V = 0, ld < V and a
+    sequence buffer without its step counters.  Nothing is written in any of them."""
+    assert MAX_VOCAB == sc.MAX_VOCAB
+    N = 3
+    out = guarded((N, 1), torch.int64, dev, fill=-7)
+    counters = guarded(N, torch.int64, dev, fill=0)
+    seq = guarded((N, 3), torch.int64, dev, fill=-1)
+
+    def untouched():
+        torch.cuda.synchronize()
+        assert (out == -7).all() and (counters == 0).all() and (seq == -1).all()
+        assert_guards_intact(out, counters, seq)
+
+    wide = torch.zeros(N, MAX_VOCAB + 1, dtype=BF, device=dev)
+    with pytest.raises(ValueError, match=f"at most {MAX_VOCAB} columns"):
+        sample_logits(wide, temperature=1.0, counters=counters, out_tok=out)
+    untouched()
+    V = 1000
+    logits = strided(config_rows(2)[:N])
+    ld = logits.stride(0)
+
+    def native(**over):
+        kw = dict(logits=logits.data_ptr(), counters=counters.data_ptr(), u=None, out_tok=out.data_ptr(), done=None,
+                  seq=None, step=None, len=None, ld=ld, seq_ld=0, eos=-1, N=N, V=V, top_k=0, temperature=1.0,
+                  top_p=1.0, seed_lo=0, seed_hi=0)
+        kw.update(over)
+        _lib.call("dpc_sample", _lib.SampleArgs(**kw), logits.device)
+
+    for over in (dict(V=0), dict(V=MAX_VOCAB + 1, ld=MAX_VOCAB + 64), dict(ld=V - 1),
+                 dict(seq=seq.data_ptr(), seq_ld=3)):
+        with pytest.raises(RuntimeError, match="dpc_sample launch failed: hipError 1$"):
+            native(**over)
+        untouched()
+    native()  # the same arguments without the fault are taken
+    torch.cuda.synchronize()
+    assert (counters == 1).all() and ((out >= 0) & (out < V)).all() and (seq == -1).all()
+    assert_guards_intact(out, counters, seq)
 
 
 @pytest.mark.parametrize("V", [7, 1000, 50257])
