@@ -255,7 +255,9 @@ __device__ __forceinline__ void g_load(uint4 (&r)[4], const bf16_t* __restrict__
       const bf16_t* src = KMAJ ? P + (long long)(mn0 + row) * ld + (k0 + col)
                                : P + (long long)(k0 + row) * ld + (mn0 + col);
       v = *reinterpret_cast<const uint4*>(src);
-      if (KMAJ && clim - col < 8) {  // K tail inside a chunk (K % 8 != 0): zero the rest
+      // the operand's extent ends inside this chunk (k-major: K % 8 != 0; mn-major: an operand
+      // stored with fewer columns than the product has rows): zero the rest
+      if (clim - col < 8) {
         const int keep = clim - col;
         unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll

@@ -213,11 +213,18 @@ inline bool plain_epilogue(const GemmArgs& a) {
   return !a.bias && !a.residual && !a.aux_in && !a.aux_out && !a.colsum && !a.act && !a.act_bwd;
 }
 
+// An mn-major operand holds every logical row of the product as a column.  The descriptor-bounded
+// loads (v2 / v3 and the persistent families) end an operand at its last byte, not at the end of a
+// stored row: the columns past a_c (b_c) of a k-row are whatever follows them in memory, which
+// only the register-staged kernel's predicates read as zeros.
+inline bool mn_cols_ok(const GemmArgs& a) { return (a.a_kmaj || a.a_c >= a.M) && (a.b_kmaj || a.b_c >= a.N); }
+
 // v2 / v3 requirements: a k-major operand must hold exactly K (% 64) columns (its k-tail is not
-// zeroed by the descriptor), N % 4 == 0 and 16-B aligned f32 epilogue operands (vector
-// epilogue), every operand inside a 31-bit byte range.
+// zeroed by the descriptor), an mn-major one every logical column (mn_cols_ok), N % 4 == 0 and
+// 16-B aligned f32 epilogue operands (vector epilogue), every operand inside a 31-bit byte range.
 inline bool gemm2_ok(const GemmArgs& a) {
-  const bool kmaj_ok = (!a.a_kmaj || (a.a_c == a.K && a.K % 64 == 0)) && (!a.b_kmaj || (a.b_c == a.K && a.K % 64 == 0));
+  const bool kmaj_ok = (!a.a_kmaj || (a.a_c == a.K && a.K % 64 == 0)) && (!a.b_kmaj || (a.b_c == a.K && a.K % 64 == 0)) &&
+                       mn_cols_ok(a);
   return kmaj_ok && a.N % 4 == 0 && operand_bytes(a.a_r, a.a_c, a.lda) > 0 && operand_bytes(a.b_r, a.b_c, a.ldb) > 0 &&
          a.K > 0 && a.ldc % 4 == 0 && a.ldr % 4 == 0 && a.ld_aux_in % 4 == 0 && a.ld_aux_out % 4 == 0 &&
          al(a.C, a.out_f32 ? 16 : 8) && al(a.bias, 16) && al(a.residual, 16) && al(a.aux_in, 8) && al(a.aux_out, 8) &&
@@ -226,10 +233,11 @@ inline bool gemm2_ok(const GemmArgs& a) {
 
 // Whether the persistent families take this product: k-major operands hold exactly K columns
 // with K % 32 == 0 (a slice never straddles a row end; mn-major operands end at row K, so their
-// last slice reads zeros past it), N % 8 == 0, 16-B aligned C / bias / residual, 8-B aligned aux.
+// last slice reads zeros past it, and hold every logical column: mn_cols_ok), N % 8 == 0, 16-B
+// aligned C / bias / residual, 8-B aligned aux.
 inline bool gemm7_ok(const GemmArgs& a) {
   const bool kmaj_ok = (!a.a_kmaj || (a.a_c == a.K && a.K % 32 == 0)) && (!a.b_kmaj || (a.b_c == a.K && a.K % 32 == 0)) &&
-                       (a.a_kmaj || a.a_r == a.K) && (a.b_kmaj || a.b_r == a.K);
+                       (a.a_kmaj || a.a_r == a.K) && (a.b_kmaj || a.b_r == a.K) && mn_cols_ok(a);
   return kmaj_ok && a.K > 0 && operand_bytes(a.a_r, a.a_c, a.lda) > 0 && operand_bytes(a.b_r, a.b_c, a.ldb) > 0 &&
          a.N % 8 == 0 && a.ldc % 8 == 0 && a.ldr % 4 == 0 && a.ld_aux_in % 4 == 0 && a.ld_aux_out % 4 == 0 &&
          al(a.C, 16) && al(a.bias, 16) && al(a.residual, 16) && al(a.aux_in, 8) && al(a.aux_out, 8) && al(a.colsum, 4);

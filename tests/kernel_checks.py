@@ -38,6 +38,25 @@ MARGIN_ATTN = 3.0  # flash attention rounds P to bf16 (measured 1.3x the ideal f
 # element error; the constants are those x 1.5.
 MARGIN_ATTN_DK_ROWS = 10.4
 MARGIN_ATTN_DK_ELEM = 8.7
+# dq and dk of the f32 attention at the edge lengths (test_gemm_forms_gpu.py: test_attention_f32_edges;
+# its forward measured 0.78 x and dv 1.82 x the ideal floor, inside MARGIN).  attention_f32.hip's
+# forward sums its scores in f64, so the o and lse it hands the backward are those of the exact
+# scores, while the backward forms the scores again with one f32 accumulator over head_dim and
+# P = exp2(s c - lse log2(e)) from them.  The ideal takes one and the same f32 s in both directions:
+# its score rounding drops out of P = exp(s - lse), its P sums to 1 over a row like the P inside
+# its o, and delta = rowsum(dO o) meets dP = dO V^T with matching roundings.  In the kernel the two
+# roundings are independent, which shows where dS = P (dP - delta) is a near-cancellation over few
+# terms: the last key of a causal sequence, seen by one query (dk of token 199 at hd 32, S 200:
+# |dk row| 1e-3 against a typical 0.8, error 2.5e-6 of it against the ideal's 6.4e-7), and the
+# queries with one or two keys (dq of token 1 at hd 128, S 129: 2.3e-6 against 6.9e-7).  Plain f32
+# math handed the KERNEL's o and lse gives the kernel's figures: dk 3.86 x (3.69 x with the
+# exponent formed in log2 units as the kernel does) against the kernel's 3.73 x at hd 32, S 200;
+# dq 1.92 x (2.13 x) against 2.52 x at hd 128, S 129 and 1.57 x (1.82 x) against 2.11 x at hd 64,
+# S 129 without the causal mask; handed the ideal's o with the kernel's lse it gives 1.35 x, 1.05 x
+# and 1.40 x.  Measured on the MI355X over the 33 cases, against the plain-f32 ideal's worst row:
+# dq 2.52 x, dk 3.73 x; the constants are those x 1.25, rounded up to one decimal.
+MARGIN_ATTN_F32_DQ = 3.2
+MARGIN_ATTN_F32_DK = 4.7
 GELU_LIPSCHITZ = 1.13  # max |gelu'| (and > max |gelu''|)
 
 # quiet-NaN patterns for the float types (a kernel that READS a guard poisons its output too),

@@ -114,6 +114,12 @@ def cases() -> list:
     for dims in ("16000x3072x768", "10000x2048x576", "65472x768x3072", "4096x4352x512"):
         out += [f"{dims}:{call} gimpl=24" for call in ("kk:h:20:bx", f"km:h:02:c{WS}", "kk:f:20:bxr", "kk:h:20:bx deriv=1",
                                                        "km:h:03:c", "kk:h:00:")]
+    # an mn-major operand stored with fewer columns than the product has rows (A) or columns (B):
+    # the descriptor-bounded loads would read what follows the stored columns, so the
+    # register-staged kernel runs it, whatever is forced (tests/gemm_forms.py: short_a_mn, short_b_mn)
+    for forced in ("", " gimpl=2", " gimpl=10", " gimpl=20", " gimpl=26"):
+        out += [short + forced for short in ("96x264x192:mk:h:00: ac=77", "96x264x192:mm:f:00: ac=72" + WS,
+                                             "77x96x192:km:h:00: bc=72", "77x96x192:km:f:00: bc=77" + WS)]
     return list(dict.fromkeys(out))  # (a few cases belong to two groups)
 
 

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 from kernel_checks import (GELU_LIPSCHITZ, MARGIN, MARGIN_ATTN, assert_elem_bound, assert_guards_intact,
                            assert_elem_close, assert_local_close, attention_bwd_plain, attention_plain, gemm_elem_bound, guarded)
+from gemm_forms import GEMM_SHAPES, IMPLS, LAYOUTS, _store, dact64, dgelu64, gelu64, gemm_data
 from mem_cases import check_cross_entropy, first_argmax
 
 from distributed_pytorch_cookbook_amd.ops import _lib
@@ -31,83 +32,12 @@ dev = "cuda"
 BF, F32 = torch.bfloat16, torch.float32
 
 
-def gelu64(z):
-    return F.gelu(z.double(), approximate="tanh")
-
-
-def dgelu64(z):
-    z = z.double()
-    k0, k1 = math.sqrt(2.0 / math.pi), 0.044715
-    t = torch.tanh(k0 * (z + k1 * z ** 3))
-    return 0.5 * (1 + t) + 0.5 * z * (1 - t * t) * k0 * (1 + 3 * k1 * z * z)
-
-
-def dact64(z, act):
-    return dgelu64(z) if act == 2 else (z.double() > 0).double()
-
-
 def _ld(n):
     """A leading dimension past the row: the next multiple of 8, and 8 more."""
     return (n + 7) // 8 * 8 + 8
 
 
-def _store(x, kmaj):
-    """Operand storage as the model lays it out: k-major rows (or mn-major columns) padded to a
-    multiple of 8 elements."""
-    r, c = x.shape
-    if kmaj:
-        buf = torch.zeros(r, (c + 7) // 8 * 8, device=dev, dtype=x.dtype)
-        buf[:, :c] = x
-        return buf[:, :c]
-    buf = torch.zeros(c, (r + 7) // 8 * 8, device=dev, dtype=x.dtype)
-    buf[:, :r] = x.t()
-    return buf[:, :r]
-
-
 # ---------------------------------------------------------------- GEMM
-LAYOUTS = [(True, True), (True, False), (False, False), (False, True)]
-IMPLS = [1, 2, 3, 4, 10, 16, 17, 19, 20, 21, 22, 25, 26]
-GEMM_SHAPES = [(1, 8, 8),          # the smallest legal product
-               (300, 264, 136),    # one full tile + tails in M, N and K
-               (513, 520, 200),    # several tiles, tails everywhere
-               # K % 64 == 0: with a k-major operand the persistent 256 x 256 kernels (and the
-               # LDS-DMA 128 x 128 ones) hand every K above to the register-staged kernel; this
-               # one they run themselves, on ragged M and N
-               (300, 264, 192)]
-_gemm_cache = {}
-
-
-def gemm_data(M, N, K, dtype=BF):
-    """Operands and the f64 results of every epilogue form, computed once per shape (shared by
-    the implementations and layouts, never modified)."""
-    key = (M, N, K, dtype)
-    if key in _gemm_cache:
-        return _gemm_cache[key]
-    g = torch.Generator(device=dev).manual_seed(M * 1000003 + N * 1009 + K)
-
-    def rn(*s):
-        return torch.randn(*s, device=dev, generator=g)
-
-    d = {}
-    d["a"] = a = rn(M, K).to(dtype)
-    d["b"] = b = (rn(N, K) / math.sqrt(K)).to(dtype)  # pre-activations of order 1: GELU's bend
-    d["bias"] = bias = rn(N)
-    d["res"] = res = rn(M, N)
-    d["z"] = z = rn(M, N).bfloat16()
-    d["acc0"] = acc0 = rn(M, N)
-    P = a.double() @ b.double().t()
-    z1 = P + bias.double()
-    d["plain"] = P
-    d["pre"] = z1
-    d["gelu"] = gelu64(z1)
-    d["dgelu"] = dgelu64(z1)
-    d["relu_res"] = torch.relu(z1) + res.double()
-    d["act_bwd"] = P * dgelu64(z)
-    d["acc"] = acc0.double() + P
-    _gemm_cache[key] = d
-    return d
-
-
 def _g(M, N, dtype, fill=None):
     return guarded((M, N), dtype, dev, ld=N + 8, fill=fill)
 
