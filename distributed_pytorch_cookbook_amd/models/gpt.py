@@ -304,7 +304,7 @@ class TransformerDecoderLM(nn.Module):
         """HIP-graph one-token decode step over ``cache`` (None for a sharded store).  For a ragged
         cache the graph may end in ``sampler`` (``ops/sample.py:Sampler``)."""
         from ..parallel.store import LocalStore
-        from ..ops.attention import DECODE_MAX_S, decode_supported
+        from ..ops.attention import decode_supported
         from .decode import GraphDecoder
         from .fused import ensure_store
 
@@ -314,8 +314,8 @@ class TransformerDecoderLM(nn.Module):
         # does not handle) decodes eagerly instead -- the torch fallback reads the length on
         # the host, which a graph capture does not allow
         attn = self.decoder.layers[0].attn
-        if (not isinstance(store, LocalStore) or cache.capacity > DECODE_MAX_S
-                or store.compute_dtype != torch.bfloat16 or not decode_supported(attn.head_dim)):
+        if (not isinstance(store, LocalStore) or store.compute_dtype != torch.bfloat16
+                or not decode_supported(attn.head_dim)):
             return None
         return GraphDecoder(self, cache, sampler)
 

@@ -199,6 +199,12 @@ class DecodeAttnArgs(ctypes.Structure):
     ]
 
 
+class DecodeSplitArgs(ctypes.Structure):
+    """``decode_split.hip:DecodeSplitArgs``: DecodeAttnArgs plus the partials' workspace
+    (f32 [N*H][nsplit][hd + 2], None at nsplit 1) and the split count."""
+    _fields_ = DecodeAttnArgs._fields_ + [("ws", P), ("nsplit", c_int)]
+
+
 class SampleArgs(ctypes.Structure):
     """``sample.hip:SampleArgs``."""
     _fields_ = [
@@ -230,6 +236,7 @@ class GemvArgs(ctypes.Structure):
 
 _FUNCS = {
     "dpc_decode_attn": DecodeAttnArgs,
+    "dpc_decode_attn_split": DecodeSplitArgs,
     "dpc_gemv": GemvArgs,
     "dpc_sample": SampleArgs,
     "dpc_embedding_bwd_sorted": EmbBwdArgs,
@@ -297,6 +304,8 @@ def lib() -> ctypes.CDLL:
             handle.dpc_occupy.restype = c_int
             handle.dpc_embedding_bwd_ws.argtypes = [c_int, c_int]
             handle.dpc_embedding_bwd_ws.restype = ctypes.c_ulonglong
+            handle.dpc_decode_split_keys_per_pass.argtypes = [c_int]
+            handle.dpc_decode_split_keys_per_pass.restype = c_int
             handle.dpc_grad_sumsq_max_blocks.argtypes = []
             handle.dpc_grad_sumsq_max_blocks.restype = c_int
             handle.dpc_grad_sumsq_trip.argtypes = []

@@ -228,22 +228,43 @@ def _attn_bwd_hip(dout, qkv, o, lse, N, S, heads, kd, pad_mask, causal, scale, d
     return dqkv
 
 
-DECODE_MAX_S = 16384  # csrc/decode.hip: LDS score buffer
+DECODE_MAX_S = 16384  # csrc/decode.hip (the one-workgroup kernel): LDS score buffer
+DECODE_MAX_SPLITS = 64  # csrc/decode_split.hip: DS_MAX_SPLITS
+# the fewest keys of cache capacity worth a workgroup of the split kernel (docs/GENERATION.md has
+# the measurement); at least 160, so that caches of up to 319 rows plan one split
+DECODE_SPLIT_MIN_KEYS = 256
 
 
 def decode_supported(head_dim: int) -> bool:
-    """Head sizes the decode kernel takes (16-B chunks of a row, at most one per thread)."""
+    """Head sizes the decode kernels take (16-B chunks of a row, at most 32 per row)."""
     return head_dim > 0 and head_dim % 8 == 0 and head_dim <= 256
 
 
-def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=False):
+def decode_splits(N: int, H: int, Smax: int, cus: int) -> int:
+    """How many workgroups share one (sequence, head)'s keys: enough to give each of ``cus``
+    compute units one, with at least DECODE_SPLIT_MIN_KEYS of the cache capacity each."""
+    want = -(-cus // max(1, N * H))
+    return max(1, min(want, Smax // DECODE_SPLIT_MIN_KEYS, DECODE_MAX_SPLITS))
+
+
+def decode_split_keys_per_pass(head_dim: int) -> int:
+    """Keys one workgroup of the split kernel covers per pass; a split's range starts at a
+    multiple of it (``csrc/decode_split.hip``)."""
+    return int(_lib.lib().dpc_decode_split_keys_per_pass(int(head_dim)))
+
+
+def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=False, splits=None):
     """One new token per sequence against a KV cache: appends its key / value at
     ``length`` (device int64 [1], cached tokens so far) and returns o [N, H*hd].
     ``per_seq``: ``length`` is int64 [N], one per sequence (a ragged batch); a sequence whose
     cache is full (``length[n] >= S_max``) appends nothing and gets a zero output row.
 
-    qkv [N, 3*H*hd]; kc, vc [N, S_max, H*hd].  HIP path: ``dpc_decode_attn``
-    (``csrc/decode.hip``); reads the length on the device, so it can be graph-captured.
+    qkv [N, 3*H*hd]; kc, vc [N, S_max, H*hd].  HIP path, the length read on the device so that
+    the call can be graph-captured: ``decode_splits`` workgroups per (sequence, head) over
+    contiguous key ranges, partials combined by a second launch (``dpc_decode_attn_split``,
+    ``csrc/decode_split.hip``; any ``S_max``); a plan of one split with ``S_max <= DECODE_MAX_S``
+    runs ``dpc_decode_attn`` (``csrc/decode.hip``).  ``splits``: that many splits of the split
+    kernel, 1 included (tests, timing); the torch path ignores it.
     """
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     N, E = qkv.shape[0], heads * head_dim
@@ -267,14 +288,24 @@ def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=F
         vf = vc[:, :pos + 1].float().reshape(N, pos + 1, heads, head_dim).transpose(1, 2)
         p = torch.softmax((qf @ kf.transpose(-1, -2)) * scale, -1)
         return (p @ vf).reshape(N, E).to(qkv.dtype)
+    if splits is None:
+        plan = decode_splits(N, heads, Smax, torch.cuda.get_device_properties(qkv.device).multi_processor_count)
+        split_kernel = plan > 1 or Smax > DECODE_MAX_S
+    else:
+        plan, split_kernel = int(splits), True
     if (qkv.stride(1) != 1 or kc.shape != (N, Smax, E) or vc.shape != kc.shape or not kc.is_contiguous()
             or not vc.is_contiguous() or kc.dtype != torch.bfloat16 or vc.dtype != torch.bfloat16
-            or not decode_supported(head_dim) or Smax > DECODE_MAX_S
+            or not decode_supported(head_dim) or not 1 <= plan <= DECODE_MAX_SPLITS
             or qkv.stride(0) % 8 or qkv.data_ptr() % 16 or length.dtype != torch.int64):
         raise ValueError("decode_attention: unsupported layout")
     o = torch.empty(N, E, device=qkv.device, dtype=torch.bfloat16)
-    args = _lib.DecodeAttnArgs(qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), o=o.data_ptr(),
-                               len=length.data_ptr(), ldqkv=qkv.stride(0), ldo=E, N=N, H=heads,
-                               hd=head_dim, Smax=Smax, scale=scale, per_seq=int(bool(per_seq)))
-    _lib.call("dpc_decode_attn", args, qkv.device)
+    common = dict(qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), o=o.data_ptr(),
+                  len=length.data_ptr(), ldqkv=qkv.stride(0), ldo=E, N=N, H=heads,
+                  hd=head_dim, Smax=Smax, scale=scale, per_seq=int(bool(per_seq)))
+    if not split_kernel:
+        _lib.call("dpc_decode_attn", _lib.DecodeAttnArgs(**common), qkv.device)
+        return o
+    # the partials live like o: allocated per call, so a capture keeps them in the graph's pool
+    ws = torch.empty(N * heads * plan * (head_dim + 2), device=qkv.device, dtype=torch.float32) if plan > 1 else None
+    _lib.call("dpc_decode_attn_split", _lib.DecodeSplitArgs(ws=_lib.ptr(ws), nsplit=plan, **common), qkv.device)
     return o
