@@ -3,8 +3,8 @@
 
 Same kernels as the training forward (``models/fused.py``: LayerNorm, QKV / FFN GEMMs with fused
 epilogues, the LM head) with the layers' self-attention replaced by one of two attends over the
-cache: a block of new tokens with the length on the host (prefill, eager steps), or one token per
-sequence with the lengths on the device (the graphed step).
+cache: a block of new tokens (prefill into an empty cache, a block appended to a cache that holds
+tokens, eager steps), or one token per sequence with the lengths on the device (the graphed step).
 """
 from __future__ import annotations
 
@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from ..ops.attention import attention_fwd, decode_attention
+from ..ops.attention import append_attention, attention_fwd, decode_attention
 from ..ops.gemm import act_code
 from .fused import _layer_forward, ensure_store, head_logits, last_rows, run_embeddings
 
@@ -56,6 +56,14 @@ class KVCache:
         else:
             self.len_t.fill_(self.len)
 
+    def set_shared_start(self, start: int) -> None:
+        """Every sequence at ``start`` (a ragged cache too): where the next block of a chunked
+        prefill goes; ``set_lengths`` gives the sequences their own lengths afterwards."""
+        self.len = start
+        if self.ragged:
+            self.lens = [start] * len(self.lens)
+        self.len_t.fill_(start)
+
     def positions(self, N: int) -> torch.Tensor:
         """Position ids [N, 1] of the next token, read from the device lengths."""
         return self.len_t.view(N, 1) if self.ragged else self.len_t.expand(N, 1)
@@ -65,13 +73,16 @@ def _block_attend(qkv, cache, li, H, hd):
     """Append the K/V of the n new tokens per sequence (qkv [N*n, 3*H*hd]) to layer li's cache at
     the host length ``cache.len`` and attend to every cached key.
 
-    Prefill (empty cache) is the flash-attention kernel over the n tokens; a decode step is
-    n queries against ``start + n`` keys -- a memory-bound read of the cache (GEMV-shaped,
-    no tiles to fill), done as two batched products in f32."""
+    Prefill (empty cache) is the flash-attention kernel over the n tokens; a block of n > 1 tokens
+    into a cache that holds some is the append kernel, which reads the start(s) from ``len_t``
+    (``ops/attention.py:append_attention``); an eager one-token step is one query against
+    ``start + 1`` keys -- a memory-bound read of the cache, done as two batched products in f32."""
     E = H * hd
     N = cache.k[li].shape[0]
     n = qkv.shape[0] // N
     start = cache.len
+    if start > 0 and n > 1:
+        return append_attention(qkv, cache.k[li], cache.v[li], cache.len_t, n, H, hd, per_seq=cache.ragged), None
     L = start + n
     q3 = qkv.view(N, n, 3, E)
     cache.k[li][:, start:L] = q3[:, :, 1]
@@ -81,10 +92,7 @@ def _block_attend(qkv, cache, li, H, hd):
     q = q3[:, :, 0].float().reshape(N, n, H, hd).transpose(1, 2)             # [N, H, n, hd]
     k = cache.k[li][:, :L].float().reshape(N, L, H, hd).transpose(1, 2)     # [N, H, L, hd]
     v = cache.v[li][:, :L].float().reshape(N, L, H, hd).transpose(1, 2)
-    sc = (q @ k.transpose(-1, -2)) * (1.0 / math.sqrt(hd))                  # [N, H, n, L]
-    if n > 1:  # causal inside the new block: query i sees keys < start + i + 1
-        qi = torch.arange(n, device=qkv.device)[:, None] + start
-        sc = sc.masked_fill(torch.arange(L, device=qkv.device)[None, :] > qi, float("-inf"))
+    sc = (q @ k.transpose(-1, -2)) * (1.0 / math.sqrt(hd))                  # [N, H, 1, L]
     o = torch.softmax(sc, -1) @ v                                            # [N, H, n, hd]
     return o.transpose(1, 2).reshape(N * n, E).to(qkv.dtype), None
 
@@ -128,28 +136,80 @@ def decode_step(model, store, cache, tok, sampler=None):
     return logits.reshape(N, 1, -1)
 
 
-def kv_decode_forward(model, input_ids, position_ids, cache, lens=None):
+def _last_valid_rows(x, N, n, lens, dev):
+    """Row ``lens[s] - 1`` of each sequence's n rows of x [N*n, D]: [N, D]."""
+    last = (torch.tensor(lens, dtype=torch.int64) - 1).to(dev)
+    return x.view(N, n, -1)[torch.arange(N, device=dev), last].contiguous()
+
+
+def prefill_chunked(model, store, input_ids, position_ids, cache, lens, chunk):
+    """The prompt into an empty cache in blocks of ``chunk`` tokens, which bounds the activations
+    to one block's: block 0 through the flash forward, block c through the append kernel at the
+    shared start ``c * chunk`` (a ragged cache too: right-padded positions land beyond ``lens[s]``
+    as in the one-shot prefill).  The hidden row ``lens[s] - 1`` of each sequence is kept from the
+    block that holds it and the LM head runs once on [N, D]; the lengths are set at the end."""
+    N, n = input_ids.shape
+    dev = input_ids.device
+    rows = None
+    try:
+        for c0 in range(0, n, chunk):
+            c1 = min(n, c0 + chunk)
+            cache.set_shared_start(c0)
+            x = run_embeddings(model, store, input_ids[:, c0:c1], position_ids[:, c0:c1], False)
+            x = _run_layers(model, store, x, N, c1 - c0, cache, _block_attend).view(N, c1 - c0, -1)
+            if rows is None:
+                rows = torch.empty(N, x.shape[-1], device=dev, dtype=x.dtype)
+            for s, l in enumerate(lens):
+                if c0 < l <= c1:
+                    rows[s] = x[s, l - 1 - c0]
+    except BaseException:
+        cache.set_shared_start(0)  # a failed prefill leaves the cache empty, as it found it
+        raise
+    cache.set_lengths(lens if cache.ragged else [n])
+    return head_logits(model, rows, store).reshape(N, 1, -1)
+
+
+def kv_decode_forward(model, input_ids, position_ids, cache, lens=None, prefill_chunk=0):
     """Incremental forward for decoding: runs only the new tokens (the whole prompt on the first
-    call, then one token per call) through the layers, extends ``cache`` and returns the logits
-    of the last new token, ``[N, 1, V]``; the reference recomputes the whole sequence for every
-    token (its ``utils.py:57-65``).
+    call, then one token or a block of tokens per call) through the layers, extends ``cache`` and
+    returns the logits of the last new token, ``[N, 1, V]``; the reference recomputes the whole
+    sequence for every token (its ``utils.py:57-65``).
 
     A ragged cache first takes right-padded prompts ``input_ids`` [N, S] with their true lengths
     ``lens``: the causal flash-attention forward over all S positions (no pad mask -- a valid row
     never sees a later key), K / V of every position into the cache, the logits of row
     ``lens[n] - 1`` of each sequence.  The padded positions land in the cache beyond ``lens[n]``;
     the decode kernel reads only ``j < len[n]`` and overwrites them one by one.  After that it
-    takes one token per sequence at its own position (``position_ids`` unused)."""
+    takes one token per sequence at its own position, or -- with ``lens``, the valid new tokens
+    1..n of each sequence -- a right-padded block of n tokens per sequence, each sequence's at its
+    own positions (``position_ids`` unused); pad rows past the capacity are not written.
+
+    ``prefill_chunk``: with an empty cache and ``0 < prefill_chunk < n``, the prompt runs in
+    blocks of that many tokens (``prefill_chunked``)."""
     store = ensure_store(model)
     N, n = input_ids.shape
     dev = input_ids.device
     if cache.ragged and cache.len > 0:
-        if n != 1:
-            raise ValueError("ragged KV cache: one token per step after the prefill")
-        cache.check_room(1)
-        logits = decode_step(model, store, cache, input_ids)
-        cache.advance(1)
-        return logits
+        if lens is not None:
+            lens = [int(l) for l in lens]
+            if len(lens) != N or min(lens) < 1 or max(lens) > n:
+                raise ValueError("ragged block: one length in 1..n per sequence")
+        elif n != 1:
+            raise ValueError("ragged KV cache: one token per step, or a block with lens")
+        if n == 1:  # (with lens too: every length is 1) the one-token step, each sequence at its own position
+            cache.check_room(1)
+            logits = decode_step(model, store, cache, input_ids)
+            cache.advance(1)
+            return logits
+        new = [old + l for old, l in zip(cache.lens, lens)]
+        if max(new) > cache.capacity:
+            raise ValueError(f"KV cache full ({max(new)} > {cache.capacity})")
+        max_pos = model.max_position_embeddings - 1
+        position_ids = (cache.len_t[:, None] + torch.arange(n, device=dev)).clamp_(max=max_pos)  # (pad rows)
+        x = run_embeddings(model, store, input_ids, position_ids, False)
+        x = _run_layers(model, store, x, N, n, cache, _block_attend)
+        cache.set_lengths(new)
+        return head_logits(model, _last_valid_rows(x, N, n, lens, dev), store).reshape(N, 1, -1)
     if cache.ragged:
         lens = [int(l) for l in lens]
         if len(lens) != N or min(lens) < 1 or max(lens) > n:
@@ -158,12 +218,14 @@ def kv_decode_forward(model, input_ids, position_ids, cache, lens=None):
     else:
         lens = [cache.len + n]
     cache.check_room(n)
+    if cache.len == 0 and 0 < prefill_chunk < n:
+        return prefill_chunked(model, store, input_ids, position_ids, cache, lens if cache.ragged else [n] * N,
+                               prefill_chunk)
     x = run_embeddings(model, store, input_ids, position_ids, False)
     x = _run_layers(model, store, x, N, n, cache, _block_attend)
     cache.set_lengths(lens)
     if cache.ragged:
-        last = (torch.tensor(lens, dtype=torch.int64) - 1).to(dev)
-        rows = x.view(N, n, -1)[torch.arange(N, device=dev), last].contiguous()
+        rows = _last_valid_rows(x, N, n, lens, dev)
     else:
         rows = last_rows(x, N, n)
     return head_logits(model, rows, store).reshape(N, 1, -1)

@@ -291,14 +291,16 @@ class TransformerDecoderLM(nn.Module):
         return KVCache(self, batch_size, max_len, next(self.parameters()).device,
                        ensure_store(self).compute_dtype, ragged)
 
-    def decode(self, input_ids, position_ids, cache, lens=None):
+    def decode(self, input_ids, position_ids, cache, lens=None, prefill_chunk=0):
         """Logits ``[N, 1, V]`` of the last of the new tokens, attending over ``cache`` (extended).
         A ragged cache takes right-padded prompts with their true lengths ``lens`` first (logits of
-        row ``lens[n] - 1``), then one token per sequence at its own position (``position_ids``
-        unused: the positions are the cache lengths)."""
+        row ``lens[n] - 1``), then one token per sequence at its own position, or a right-padded
+        block with ``lens`` valid new tokens per sequence (``position_ids`` unused: the positions
+        are the cache lengths).  ``prefill_chunk``: a prompt longer than that goes into an empty
+        cache in blocks of that many tokens (0: in one)."""
         from .decode import kv_decode_forward
 
-        return kv_decode_forward(self, input_ids, position_ids, cache, lens)
+        return kv_decode_forward(self, input_ids, position_ids, cache, lens, prefill_chunk)
 
     def graph_decoder(self, cache, sampler=None):
         """HIP-graph one-token decode step over ``cache`` (None for a sharded store).  For a ragged

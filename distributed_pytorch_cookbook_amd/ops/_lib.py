@@ -205,6 +205,18 @@ class DecodeSplitArgs(ctypes.Structure):
     _fields_ = DecodeAttnArgs._fields_ + [("ws", P), ("nsplit", c_int)]
 
 
+class AppendAttnArgs(ctypes.Structure):
+    """``append_attn.hip:AppendAttnArgs``; ws: f32 [N*n*H][nsplit][hd + 4], None at nsplit 1."""
+    _fields_ = [
+        ("qkv", P), ("kc", P), ("vc", P), ("o", P), ("len", P),
+        ("ldqkv", LL), ("ldo", LL),
+        ("N", c_int), ("n", c_int), ("H", c_int), ("hd", c_int), ("Smax", c_int),
+        ("scale", c_float),
+        ("per_seq", c_int),
+        ("ws", P), ("nsplit", c_int),
+    ]
+
+
 class SampleArgs(ctypes.Structure):
     """``sample.hip:SampleArgs``."""
     _fields_ = [
@@ -237,6 +249,7 @@ class GemvArgs(ctypes.Structure):
 _FUNCS = {
     "dpc_decode_attn": DecodeAttnArgs,
     "dpc_decode_attn_split": DecodeSplitArgs,
+    "dpc_append_attn": AppendAttnArgs,
     "dpc_gemv": GemvArgs,
     "dpc_sample": SampleArgs,
     "dpc_embedding_bwd_sorted": EmbBwdArgs,
@@ -306,6 +319,8 @@ def lib() -> ctypes.CDLL:
             handle.dpc_embedding_bwd_ws.restype = ctypes.c_ulonglong
             handle.dpc_decode_split_keys_per_pass.argtypes = [c_int]
             handle.dpc_decode_split_keys_per_pass.restype = c_int
+            handle.dpc_append_attn_tiles.argtypes = [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+            handle.dpc_append_attn_tiles.restype = None
             handle.dpc_grad_sumsq_max_blocks.argtypes = []
             handle.dpc_grad_sumsq_max_blocks.restype = c_int
             handle.dpc_grad_sumsq_trip.argtypes = []

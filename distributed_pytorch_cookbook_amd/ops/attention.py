@@ -29,6 +29,7 @@ CPU / fp32 path: the same math with torch ops (test oracle).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -308,4 +309,94 @@ def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=F
     # the partials live like o: allocated per call, so a capture keeps them in the graph's pool
     ws = torch.empty(N * heads * plan * (head_dim + 2), device=qkv.device, dtype=torch.float32) if plan > 1 else None
     _lib.call("dpc_decode_attn_split", _lib.DecodeSplitArgs(ws=_lib.ptr(ws), nsplit=plan, **common), qkv.device)
+    return o
+
+
+APPEND_MAX_SPLITS = 64  # csrc/append_attn.hip: APPEND_MAX_SPLITS
+APPEND_SPLIT_MIN_TILES = 4  # the fewest key tiles of cache capacity worth a workgroup of their own
+
+
+def append_attn_tiles(head_dim: int = 64):
+    """(QB, KT) of ``csrc/append_attn.hip``: query rows per workgroup and keys per tile; a split's
+    range starts at a multiple of KT."""
+    qb, kt = ctypes.c_int(), ctypes.c_int()
+    _lib.lib().dpc_append_attn_tiles(int(head_dim), ctypes.byref(qb), ctypes.byref(kt))
+    return qb.value, kt.value
+
+
+def append_splits(N: int, H: int, n: int, Smax: int, cus: int) -> int:
+    """How many workgroups share the keys of one query tile of one (sequence, head): 1 when the
+    query tiles alone give each of ``cus`` compute units a workgroup, else enough to, with at least
+    APPEND_SPLIT_MIN_TILES key tiles of the cache capacity each.  Planned from the capacity, never
+    from the device length: the launch shape is the same on every replay."""
+    qb, kt = append_attn_tiles()
+    wgs = max(1, N * H * -(-n // qb))
+    want = -(-cus // wgs)
+    return max(1, min(want, -(-Smax // kt) // APPEND_SPLIT_MIN_TILES, APPEND_MAX_SPLITS))
+
+
+def _append_torch(qkv, kc, vc, start, n, heads, head_dim, scale):
+    """The materialised path at one shared ``start`` (host int): f32 scores [N, H, m, start + m] over
+    the up-cast cache prefix, m = the new tokens that fit the capacity; the rest get zero rows."""
+    N, Smax, E = kc.shape
+    o = torch.zeros(N, n, E, device=qkv.device, dtype=qkv.dtype)
+    m = min(n, Smax - start) if 0 <= start < Smax else 0
+    if m <= 0:
+        return o.reshape(N * n, E)
+    L = start + m
+    q3 = qkv[:, :3 * E].reshape(N, n, 3, E)[:, :m]  # (qkv may be wider than 3 E, or strided)
+    kc[:, start:L] = q3[:, :, 1]
+    vc[:, start:L] = q3[:, :, 2]
+    q = q3[:, :, 0].float().reshape(N, m, heads, head_dim).transpose(1, 2)   # [N, H, m, hd]
+    k = kc[:, :L].float().reshape(N, L, heads, head_dim).transpose(1, 2)     # [N, H, L, hd]
+    v = vc[:, :L].float().reshape(N, L, heads, head_dim).transpose(1, 2)
+    sc = (q @ k.transpose(-1, -2)) * scale                                   # [N, H, m, L]
+    qi = torch.arange(m, device=qkv.device)[:, None] + start                 # query i sees keys <= start + i
+    sc = sc.masked_fill(torch.arange(L, device=qkv.device)[None, :] > qi, float("-inf"))
+    o[:, :m] = (torch.softmax(sc, -1) @ v).transpose(1, 2).reshape(N, m, E).to(qkv.dtype)
+    return o.reshape(N * n, E)
+
+
+def append_attention(qkv, kc, vc, length, n, heads, head_dim, scale=None, per_seq=False, splits=None):
+    """A block of ``n`` new tokens per sequence against a KV cache that may already hold tokens:
+    token i of sequence s sits at position p = length[s] + i (``length`` device int64 [1], or [N]
+    with ``per_seq``); its key / value go to cache row p and its output row is the softmax over
+    cache rows 0..p.  A token with p >= S_max is not written and gets a zero row.  ``length`` is
+    not advanced.  Returns o [N*n, H*hd].
+
+    qkv [N*n, 3*H*hd] token-major; kc, vc [N, S_max, H*hd].  HIP path (CUDA bf16, head_dim 32, 64
+    or 128): ``dpc_append_attn`` (``csrc/append_attn.hip``), the length read on the device so that
+    the call can be graph-captured; ``append_splits`` workgroups share the keys of a query tile,
+    their partials combined by a further launch.  ``splits``: that many, 1 included (tests, timing).
+    Anything else runs the materialised torch path, which reads the length on the host."""
+    scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
+    N, Smax, E = kc.shape[0], kc.shape[1], heads * head_dim
+    if length.numel() != (N if per_seq else 1):
+        raise ValueError("append_attention: length must be [N] with per_seq, [1] without")
+    if qkv.shape[0] != N * n or qkv.shape[1] < 3 * E:
+        raise ValueError("append_attention: qkv must hold n rows of 3*H*hd per sequence")
+    if not scale > 0:  # the kernel takes the tile maximum on raw scores and scales it afterwards
+        raise ValueError("append_attention: scale must be positive")
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and head_dim in HD_KERNELS):
+        if not per_seq:
+            return _append_torch(qkv, kc, vc, int(length), n, heads, head_dim, scale)
+        rows = qkv[:, :3 * E].reshape(N, n, 3 * E)
+        return torch.cat([_append_torch(rows[s], kc[s:s + 1], vc[s:s + 1], pos, n, heads, head_dim, scale)
+                          for s, pos in enumerate(length.tolist())])
+    if splits is None:
+        plan = append_splits(N, heads, n, Smax, torch.cuda.get_device_properties(qkv.device).multi_processor_count)
+    else:
+        plan = int(splits)
+    if (qkv.stride(1) != 1 or kc.shape != (N, Smax, E) or vc.shape != kc.shape
+            or not kc.is_contiguous() or not vc.is_contiguous() or kc.dtype != torch.bfloat16
+            or vc.dtype != torch.bfloat16 or not 1 <= plan <= APPEND_MAX_SPLITS or N * heads > 65535
+            or qkv.stride(0) % 8 or qkv.data_ptr() % 16 or length.dtype != torch.int64 or not length.is_cuda):
+        raise ValueError("append_attention: unsupported layout")
+    o = torch.empty(N * n, E, device=qkv.device, dtype=torch.bfloat16)
+    # the partials live like o: allocated per call, so a capture keeps them in the graph's pool
+    ws = torch.empty(N * n * heads * plan * (head_dim + 4), device=qkv.device, dtype=torch.float32) if plan > 1 else None
+    _lib.call("dpc_append_attn", _lib.AppendAttnArgs(
+        qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), o=o.data_ptr(), len=length.data_ptr(),
+        ldqkv=qkv.stride(0), ldo=E, N=N, n=n, H=heads, hd=head_dim, Smax=Smax, scale=scale,
+        per_seq=int(bool(per_seq)), ws=_lib.ptr(ws), nsplit=plan), qkv.device)
     return o
