@@ -246,11 +246,17 @@ class GemvArgs(ctypes.Structure):
     ]
 
 
+class SkinnyArgs(ctypes.Structure):
+    """``skinny_gemm.hip:SkinnyArgs``: GemvArgs plus the plan (ops/gemm.py:skinny_plan)."""
+    _fields_ = GemvArgs._fields_ + [("nb", c_int), ("nw", c_int)]
+
+
 _FUNCS = {
     "dpc_decode_attn": DecodeAttnArgs,
     "dpc_decode_attn_split": DecodeSplitArgs,
     "dpc_append_attn": AppendAttnArgs,
     "dpc_gemv": GemvArgs,
+    "dpc_gemm_skinny": SkinnyArgs,
     "dpc_sample": SampleArgs,
     "dpc_embedding_bwd_sorted": EmbBwdArgs,
     "dpc_gemm": GemmArgs,

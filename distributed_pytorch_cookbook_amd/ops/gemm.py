@@ -406,9 +406,16 @@ def linear_fwd(x, w, *, bias=None, act=None, residual=None, aux_out=None, out=No
                out_dtype=torch.bfloat16, aux_deriv=False):
     """y = act(x @ w^T + bias) (+ residual); x [M, K], w [N, K] (nn.Linear layout).
     ``aux_out`` receives the pre-activation, or act'(pre-activation) with ``aux_deriv``."""
-    if (x.is_cuda and x.shape[0] <= _GEMV_ROWS and aux_out is None and x.dtype == torch.bfloat16
-            and w.dtype == torch.bfloat16):
-        return _linear_fwd_few_rows(x, w, bias, act_code(act), residual, out, out_dtype)
+    if x.is_cuda and aux_out is None and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16:
+        M = x.shape[0]
+        if M <= _GEMV_ROWS:
+            return _linear_fwd_few_rows(x, w, bias, act_code(act), residual, out, out_dtype)
+        N = w.shape[0] if out is None else out.shape[-1]
+        if _SKINNY_NATIVE and M <= _SKINNY_ROWS and N <= _SKINNY_MAX_N:
+            if out is None:
+                out = torch.empty(M, w.shape[0], device=x.device, dtype=out_dtype)
+            if _skinny_ok(x, w, bias, residual, out):
+                return _linear_fwd_skinny(x, w, bias, act_code(act), residual, out, out_dtype)
     return gemm(x, w, a_kmaj=True, b_kmaj=True, bias=bias, act=act, residual=residual,
                 aux_out=aux_out, out=out, out_dtype=out_dtype, aux_deriv=aux_deriv)
 
@@ -453,6 +460,61 @@ def _linear_fwd_few_rows(x, w, bias, act, residual, out, out_dtype):
     out[:, :Nw].copy_(v)
     if N > Nw:
         out[:, Nw:].zero_()
+    return out
+
+
+# 17 .. _SKINNY_ROWS rows (decode at batch 17-64, blocks of draft tokens, chunked-prefill tails, the
+# LM head on that many last rows): still a stream of the weights, but with enough rows per weight
+# byte for the matrix cores -- csrc/skinny_gemm.hip: dpc_gemm_skinny, one workgroup per strip of
+# NB output columns with its waves splitting K, the same fused epilogue as dpc_gemv.  The training
+# dispatcher would give these products N / 256 workgroups.
+_SKINNY_MAX_ROWS = 64  # what the kernel takes
+# what linear_fwd sends it (docs/GENERATION.md, measured per shape on the MI355X): every row count
+# the kernel takes, but no product wider than _SKINNY_MAX_N columns -- the LM head over the
+# vocabulary gives the dispatcher 197 tiles, and from 32 (GPT-2 XL) or 48 (GPT-2 small) rows on
+# the dispatcher is the faster of the two there
+_SKINNY_ROWS = 64
+_SKINNY_MAX_N = 32768
+_SKINNY_NATIVE = os.environ.get("DPC_SKINNY", "1") == "1"  # 0: the dispatcher, as before (A/B only)
+SKINNY_PLANS = ((16, 8), (32, 4))  # the instantiated (columns, waves) per workgroup
+
+
+def skinny_plan(M: int, N: int, K: int, cus: int):
+    """(NB, waves) of one workgroup of the skinny kernel, from the shape alone (a captured graph
+    replays the same launch).  Every workgroup reads all of x (from L2), so a wider strip divides
+    that traffic -- at NB = 16 and M = 64 it is four times the weight bytes -- but also the
+    workgroup count: 32 columns while that still leaves a workgroup for every second one of ``cus``
+    compute units (measured: GPT-2 XL's QKV and up-projection, 150 and 200 strips of 32, run 16
+    to 22 % faster that way at every row count; GPT-2 small's up-projection, 96 strips, 19 %
+    slower), else 16 columns, whose eight waves split K further."""
+    nb, nw = SKINNY_PLANS[1]
+    return (nb, nw) if 2 * -(-N // nb) >= cus else SKINNY_PLANS[0]
+
+
+def _skinny_ok(x, w, bias, residual, out):
+    return (x.dim() == 2 and w.dim() == 2 and out.dim() == 2 and 0 < w.shape[0] and w.shape[1] == x.shape[1]
+            and out.shape[0] == x.shape[0] and out.dtype in (torch.float32, torch.bfloat16)
+            and _gemv_ok(x, w, bias, residual, out, out.shape[1])
+            and (residual is None or (residual.shape[0] >= x.shape[0] and residual.shape[1] >= w.shape[0])))
+
+
+def _linear_fwd_skinny(x, w, bias, act, residual, out, out_dtype, plan=None):
+    """``dpc_gemm_skinny`` on operands it takes (``_skinny_ok``; anything else raises).  ``plan``:
+    one of SKINNY_PLANS instead of the planner's choice (tests, measurements)."""
+    M, K = x.shape
+    Nw = w.shape[0]
+    if out is None:
+        out = torch.empty(M, Nw, device=x.device, dtype=out_dtype)
+    if not (0 < M <= _SKINNY_MAX_ROWS and _skinny_ok(x, w, bias, residual, out)):
+        raise ValueError("linear_fwd (skinny): operands the kernel does not take")
+    N = out.shape[1]
+    nb, nw = plan or skinny_plan(M, N, K, torch.cuda.get_device_properties(x.device).multi_processor_count)
+    args = _lib.SkinnyArgs(
+        x=x.data_ptr(), w=w.data_ptr(), bias=_lib.ptr(bias), residual=_lib.ptr(residual),
+        y=out.data_ptr(), ldx=x.stride(0), ldw=w.stride(0),
+        ldr=residual.stride(0) if residual is not None else 0, ldy=out.stride(0),
+        M=M, N=N, Nw=Nw, K=K, act=act, y_f32=int(out.dtype == torch.float32), nb=nb, nw=nw)
+    _lib.call("dpc_gemm_skinny", args, x.device)
     return out
 
 
