@@ -9,7 +9,10 @@ layers of a real step.  Beside each time:
 the K/V bytes the call must read, computed from the shape, and those bytes over the time.  One
 JSON line per (batch, length, variant).
 
-    python bench/decode_attn_time.py [--splits 2 4 8 16] [--lengths 1000 4000 16000 32000]
+    python bench/decode_attn_time.py [--splits 2 4 8 16] [--lengths 1000 4000 16000 32000] [--kv_dtype fp8]
+
+``--kv_dtype fp8``: the same calls over a 1-byte e4m3 cache (always the split kernel's fp8 twin;
+half the K/V bytes).
 """
 import argparse
 import json
@@ -44,7 +47,9 @@ def main():
     ap.add_argument("--splits", type=int, nargs="*", default=[], help="further forced split counts")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"])
     a = ap.parse_args()
+    fp8 = a.kv_dtype == "fp8"
     if not torch.cuda.is_available():
         raise SystemExit("decode_attn_time.py times HIP kernels: no GPU found")
     torch.manual_seed(0)
@@ -72,17 +77,19 @@ def main():
             Smax = L + 68  # the capacity bench/generate.py gives a context of L
             kc = torch.randn(N, Smax, E, device="cuda").bfloat16()
             vc = torch.randn(N, Smax, E, device="cuda").bfloat16()
+            if fp8:
+                kc, vc = A.kv_quantize_ref(kc, 1.0), A.kv_quantize_ref(vc, 1.0)
             qkv = torch.randn(N, 3 * E, device="cuda").bfloat16()
             length = torch.full((1,), L - 1, device="cuda", dtype=torch.int64)  # L keys with the new one
             plan = A.decode_splits(N, H, Smax, cus)
             variants = [("split 1", lambda: A.decode_attention(qkv, kc, vc, length, H, hd, splits=1)),
                         (f"plan {plan}", lambda: A.decode_attention(qkv, kc, vc, length, H, hd))]
-            if Smax <= A.DECODE_MAX_S:
+            if Smax <= A.DECODE_MAX_S and not fp8:
                 variants.insert(0, ("one workgroup", lambda: one_workgroup(qkv, kc, vc, length, H, hd)))
             for k in a.splits:
                 variants.append((f"split {k}", lambda k=k: A.decode_attention(qkv, kc, vc, length, H, hd, splits=k)))
             ref = None
-            kv_bytes = 2 * N * L * E * 2
+            kv_bytes = 2 * N * L * E * kc.element_size()
             for name, fn in variants:
                 o = fn().float()
                 ref = o if ref is None else ref
@@ -90,7 +97,7 @@ def main():
                 timed(g, a.iters)
                 us = [timed(g, a.iters) for _ in range(a.rounds)]
                 med = statistics.median(us)
-                print(json.dumps({"batch": N, "keys": L, "variant": name, "us_per_call": round(med, 2),
+                print(json.dumps({"kv_dtype": a.kv_dtype, "batch": N, "keys": L, "variant": name, "us_per_call": round(med, 2),
                                   "min_us": round(min(us), 2), "max_us": round(max(us), 2), "kv_bytes": kv_bytes,
                                   "kv_bytes_per_s": round(kv_bytes / (med * 1e-6)),
                                   "max_diff_vs_first": round((o - ref).abs().max().item(), 5)}), flush=True)

@@ -7,7 +7,7 @@ ms per step, and ms per token per sequence = that / B).
 
     python bench/generate.py [--model gpt2-small] [--ctx 1000] [--tokens 20]
                              [--batch 8 --temperature 0.8 --top_k 50 --top_p 0.9]
-                             [--prefill_chunk 512]
+                             [--prefill_chunk 512] [--kv_dtype fp8]
 
 ``prefill_ms``: the prompt into an empty cache (the median of three, after a warm-up prefill), in
 blocks of ``--prefill_chunk`` tokens where given (every prefill of the KV-cache sections then runs
@@ -36,7 +36,9 @@ def main():
     ap.add_argument("--top_k", type=int, default=0)
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--prefill_chunk", type=int, default=0, help="prefill in blocks of this many tokens (0: in one)")
+    ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"], help="element of the KV cache")
     a = ap.parse_args()
+    kv = {"kv_dtype": a.kv_dtype}
     p = PRESETS[a.model]
     dev = torch.device("cuda")
     torch.manual_seed(0)
@@ -61,7 +63,7 @@ def main():
         res["last_only" if last_only else "all_positions"] = (time.perf_counter() - t0) / a.tokens * 1e3
     ids = torch.randint(0, 50257, (1, a.ctx), device=dev)
     with torch.inference_mode():
-        cache = m.new_kv_cache(1, a.ctx + a.tokens + 4)
+        cache = m.new_kv_cache(1, a.ctx + a.tokens + 4, **kv)
         logits = m.decode(ids, torch.arange(a.ctx, device=dev).unsqueeze(0), cache, prefill_chunk=a.prefill_chunk)
         for i in range(0 if a.graph_only else a.tokens + 3):
             if i == 3:
@@ -76,7 +78,7 @@ def main():
     with torch.inference_mode():
         prefill = []
         for _ in range(3):
-            cache = m.new_kv_cache(1, a.ctx + a.tokens + 4)
+            cache = m.new_kv_cache(1, a.ctx + a.tokens + 4, **kv)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             logits = m.decode(ids, torch.arange(a.ctx, device=dev).unsqueeze(0), cache, prefill_chunk=a.prefill_chunk)
@@ -100,7 +102,7 @@ def main():
         lens = [a.ctx - 7 * n for n in range(B)]  # ragged: the longest prompt is ctx
         ids = torch.randint(0, 50256, (B, a.ctx), device=dev)
         with torch.inference_mode():
-            cache = m.new_kv_cache(B, a.ctx + a.tokens + 4, ragged=True)
+            cache = m.new_kv_cache(B, a.ctx + a.tokens + 4, ragged=True, **kv)
             sampler = Sampler(B, a.tokens + 4, dev, a.temperature, a.top_k, a.top_p, seed=0, eos=-1)
             sampler(m.decode(ids, None, cache, lens=lens)[:, 0])
             dec = m.graph_decoder(cache, sampler)
@@ -114,7 +116,7 @@ def main():
         batched = {"batch": B, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
                    "ms_per_step": ms, "ms_per_token_per_sequence": ms / B}
         res["kv_cache_graph_batched"] = ms
-    head = {"model": a.model, "ctx": a.ctx, "prefill_chunk": a.prefill_chunk}
+    head = {"model": a.model, "ctx": a.ctx, "prefill_chunk": a.prefill_chunk, "kv_dtype": a.kv_dtype}
     if a.graph_only:
         print(json.dumps({**head, "ms_per_token": res, "kv_cache_graph_batched": batched}))
         return

@@ -86,6 +86,9 @@ def build_parser(recipe: str = "single") -> argparse.ArgumentParser:
     p.add_argument("--top_k", type=int, default=0, help="sampling: keep the k most likely tokens, ties included (0 = off)")
     p.add_argument("--top_p", type=float, default=1.0, help="sampling: nucleus mass (1.0 = off)")
     p.add_argument("--sample_seed", type=int, default=0, help="seed of the sampler's counter-based stream")
+    p.add_argument("--kv_cache_dtype", type=str, default="bf16", choices=["bf16", "fp8"],
+                   help="KV cache of the end-of-epoch samples: the compute dtype, or 1-byte e4m3 (GPU, bf16, "
+                        "head_dim 32 / 64 / 128)")
     p.add_argument("--bucket_mb", type=float, default=128.0, help="DDP gradient bucket size")
     p.add_argument("--reduce_dtype", type=str, default="fp32", choices=["fp32", "bf16"])
     p.add_argument("--no_overlap", action="store_true", help="all-reduce after backward instead of during")

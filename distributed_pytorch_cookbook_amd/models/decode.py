@@ -12,7 +12,7 @@ import math
 
 import torch
 
-from ..ops.attention import append_attention, attention_fwd, decode_attention
+from ..ops.attention import FP8, append_attention, attention_fwd, decode_attention, kv_cache_store_fp8
 from ..ops.gemm import act_code
 from .fused import _layer_forward, ensure_store, head_logits, last_rows, run_embeddings
 
@@ -22,9 +22,23 @@ class KVCache:
     in the compute dtype (GPT-2 XL at S_max = 1024: 2 x 48 x 1024 x 1600 x 2 B = 315 MB per
     sequence).  ``ragged``: one length per sequence -- ``len_t`` is ``[N]`` with the host copy
     ``lens``, so right-padded prompts of different lengths share the batch.  ``len`` is the
-    (longest) length on the host; only the methods below assign the lengths' host copies."""
+    (longest) length on the host; only the methods below assign the lengths' host copies.
 
-    def __init__(self, model, N, S_max, device, dtype, ragged=False):
+    ``kv_dtype="fp8"``: the tensors are ``torch.float8_e4m3fn``, half the bytes (GPT-2 XL at
+    S_max = 1024: 157 MB per sequence), holding ``x / k_scale`` and ``x / v_scale`` (one host
+    float per cache each, ``ops/attention.py:kv_quantize_ref``); every attend over the cache is then
+    a HIP kernel that dequantises on the way in.  ``models/gpt.py:new_kv_cache`` checks what that
+    needs (CUDA, a bf16 local store, head_dim 32 / 64 / 128)."""
+
+    def __init__(self, model, N, S_max, device, dtype, ragged=False, kv_dtype=None, k_scale=1.0, v_scale=1.0):
+        if kv_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"KV cache: kv_dtype must be None, 'bf16' or 'fp8', not {kv_dtype!r}")
+        self.fp8 = kv_dtype == "fp8"
+        self.k_scale, self.v_scale = float(k_scale), float(v_scale)
+        if not self.fp8 and (self.k_scale != 1.0 or self.v_scale != 1.0):
+            raise ValueError("KV cache: k_scale / v_scale belong to the fp8 cache")
+        if self.fp8:
+            dtype = FP8  # (zeros: byte 0 is +0)
         self.k, self.v = [], []
         for layer in model.decoder.layers:
             E = layer.attn.heads * layer.attn.head_dim
@@ -81,8 +95,18 @@ def _block_attend(qkv, cache, li, H, hd):
     N = cache.k[li].shape[0]
     n = qkv.shape[0] // N
     start = cache.len
+    scales = dict(k_scale=cache.k_scale, v_scale=cache.v_scale) if cache.fp8 else {}
     if start > 0 and n > 1:
-        return append_attention(qkv, cache.k[li], cache.v[li], cache.len_t, n, H, hd, per_seq=cache.ragged), None
+        return append_attention(qkv, cache.k[li], cache.v[li], cache.len_t, n, H, hd, per_seq=cache.ragged,
+                                **scales), None
+    if cache.fp8:
+        # prefill: quantised rows into the cache (len_t holds the start, 0), flash attention over the
+        # prompt's own bf16 k / v; the one-token step: the decode kernel (no torch path over fp8)
+        if start > 0:
+            return decode_attention(qkv, cache.k[li], cache.v[li], cache.len_t, H, hd, per_seq=cache.ragged,
+                                    **scales), None
+        kv_cache_store_fp8(qkv, cache.k[li], cache.v[li], cache.len_t, n, H, hd, per_seq=cache.ragged, **scales)
+        return attention_fwd(qkv, N, n, H, hd, None, causal=True)
     L = start + n
     q3 = qkv.view(N, n, 3, E)
     cache.k[li][:, start:L] = q3[:, :, 1]
@@ -101,7 +125,8 @@ def _step_attend(qkv, cache, li, H, hd):
     """One query per sequence against the cache, the new key / value appended at the
     device-side length(s) by the decode kernel: no shape depends on a length, so the step
     can be graphed."""
-    return decode_attention(qkv, cache.k[li], cache.v[li], cache.len_t, H, hd, per_seq=cache.ragged), None
+    scales = dict(k_scale=cache.k_scale, v_scale=cache.v_scale) if cache.fp8 else {}
+    return decode_attention(qkv, cache.k[li], cache.v[li], cache.len_t, H, hd, per_seq=cache.ragged, **scales), None
 
 
 def _run_layers(model, store, x, N, n, cache, attend):

@@ -283,13 +283,28 @@ class TransformerDecoderLM(nn.Module):
         return fused_lm_forward(self, input_ids, position_ids, mask, targets, want_correct, dropout_seed,
                                 last_only)
 
-    def new_kv_cache(self, batch_size: int, max_len: int, ragged: bool = False):
-        """``ragged``: one cache length per sequence (prompts of different lengths in one batch)."""
+    def new_kv_cache(self, batch_size: int, max_len: int, ragged: bool = False, kv_dtype=None,
+                     k_scale: float = 1.0, v_scale: float = 1.0):
+        """``ragged``: one cache length per sequence (prompts of different lengths in one batch).
+        ``kv_dtype``: None or "bf16" -- the compute dtype, as ever -- or "fp8": 1-byte e4m3 keys and
+        values holding ``x / k_scale`` and ``x / v_scale`` (``models/decode.py:KVCache``).  The fp8
+        cache is read by HIP kernels only: it needs CUDA, a bf16 non-sharded store and head_dim 32,
+        64 or 128, and raises ``ValueError`` otherwise."""
+        from ..ops.attention import kv_fp8_supported
+        from ..parallel.store import LocalStore
         from .decode import KVCache
         from .fused import ensure_store
 
-        return KVCache(self, batch_size, max_len, next(self.parameters()).device,
-                       ensure_store(self).compute_dtype, ragged)
+        store = ensure_store(self)
+        device = next(self.parameters()).device
+        if kv_dtype == "fp8":
+            attn = self.decoder.layers[0].attn
+            if (device.type != "cuda" or not isinstance(store, LocalStore) or store.compute_dtype != torch.bfloat16
+                    or not kv_fp8_supported(attn.head_dim)):
+                raise ValueError("fp8 KV cache: needs CUDA, a bf16 non-sharded parameter store and head_dim 32, 64 "
+                                 f"or 128 (device {device}, {type(store).__name__} {store.compute_dtype}, "
+                                 f"head_dim {attn.head_dim})")
+        return KVCache(self, batch_size, max_len, device, store.compute_dtype, ragged, kv_dtype, k_scale, v_scale)
 
     def decode(self, input_ids, position_ids, cache, lens=None, prefill_chunk=0):
         """Logits ``[N, 1, V]`` of the last of the new tokens, attending over ``cache`` (extended).

@@ -217,6 +217,20 @@ class AppendAttnArgs(ctypes.Structure):
     ]
 
 
+_KV_SCALES = [("k_scale", c_float), ("k_inv", c_float), ("v_scale", c_float), ("v_inv", c_float)]
+
+
+class DecodeSplitFp8Args(ctypes.Structure):
+    """``decode_split.hip:DecodeSplitFp8Args``: DecodeSplitArgs over an e4m3 cache plus its scales
+    (``x = byte * scale``, ``byte = fp8(x * inv)``, ``inv = float32(1 / scale)``)."""
+    _fields_ = DecodeSplitArgs._fields_ + _KV_SCALES
+
+
+class AppendAttnFp8Args(ctypes.Structure):
+    """``append_attn.hip:AppendAttnFp8Args``: AppendAttnArgs over an e4m3 cache plus its scales."""
+    _fields_ = AppendAttnArgs._fields_ + _KV_SCALES
+
+
 class SampleArgs(ctypes.Structure):
     """``sample.hip:SampleArgs``."""
     _fields_ = [
@@ -255,6 +269,9 @@ _FUNCS = {
     "dpc_decode_attn": DecodeAttnArgs,
     "dpc_decode_attn_split": DecodeSplitArgs,
     "dpc_append_attn": AppendAttnArgs,
+    "dpc_decode_attn_split_fp8": DecodeSplitFp8Args,
+    "dpc_append_attn_fp8": AppendAttnFp8Args,
+    "dpc_kv_store_fp8": AppendAttnFp8Args,
     "dpc_gemv": GemvArgs,
     "dpc_gemm_skinny": SkinnyArgs,
     "dpc_sample": SampleArgs,
@@ -325,6 +342,8 @@ def lib() -> ctypes.CDLL:
             handle.dpc_embedding_bwd_ws.restype = ctypes.c_ulonglong
             handle.dpc_decode_split_keys_per_pass.argtypes = [c_int]
             handle.dpc_decode_split_keys_per_pass.restype = c_int
+            handle.dpc_decode_fp8_keys_per_pass.argtypes = [c_int]
+            handle.dpc_decode_fp8_keys_per_pass.restype = c_int
             handle.dpc_append_attn_tiles.argtypes = [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
             handle.dpc_append_attn_tiles.restype = None
             handle.dpc_grad_sumsq_max_blocks.argtypes = []

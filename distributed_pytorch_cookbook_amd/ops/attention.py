@@ -254,7 +254,68 @@ def decode_split_keys_per_pass(head_dim: int) -> int:
     return int(_lib.lib().dpc_decode_split_keys_per_pass(int(head_dim)))
 
 
-def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=False, splits=None):
+FP8 = torch.float8_e4m3fn  # the 1-byte KV cache's element (OCP e4m3, what gfx950 converts in hardware)
+FP8_MAX = 448.0
+
+
+def decode_fp8_keys_per_pass(head_dim: int) -> int:
+    """``decode_split_keys_per_pass`` of the fp8 kernel (a key row takes hd / 16 lanes)."""
+    return int(_lib.lib().dpc_decode_fp8_keys_per_pass(int(head_dim)))
+
+
+def kv_fp8_supported(head_dim: int) -> bool:
+    """Head sizes with an fp8-cache decode and append kernel."""
+    return head_dim in HD_KERNELS
+
+
+def kv_quantize_ref(x: torch.Tensor, scale: float) -> torch.Tensor:
+    """The torch twin of the kernels' quantisation, bit for bit: the f32 product with
+    float32(1 / scale), clamped to +-448 ahead of the convert (e4m3fn has no infinity: an
+    overflowing convert gives NaN), rounded to nearest even."""
+    inv = torch.tensor(1.0 / scale, dtype=torch.float32, device=x.device)
+    return (x.float() * inv).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+
+
+def _kv_scales(k_scale, v_scale, what):
+    k_scale, v_scale = float(k_scale), float(v_scale)
+    if not (math.isfinite(k_scale) and math.isfinite(v_scale) and k_scale > 0 and v_scale > 0):
+        raise ValueError(f"{what}: k_scale and v_scale must be positive and finite")
+    return dict(k_scale=k_scale, k_inv=1.0 / k_scale, v_scale=v_scale, v_inv=1.0 / v_scale)
+
+
+def _check_fp8(what, qkv, kc, vc, N, Smax, E, head_dim, length):
+    """An fp8 cache pair takes CUDA bf16 qkv and the bf16 kernels' layout at head_dim 32 / 64 / 128;
+    there is no torch path."""
+    if kc.dtype != vc.dtype:
+        raise ValueError(f"{what}: kc and vc must share a dtype")
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and kc.is_cuda and vc.is_cuda):
+        raise ValueError(f"{what}: an fp8 cache needs CUDA bf16 qkv")
+    if (qkv.stride(1) != 1 or kc.shape != (N, Smax, E) or vc.shape != kc.shape or not kc.is_contiguous()
+            or not vc.is_contiguous() or not kv_fp8_supported(head_dim) or qkv.stride(0) % 8
+            or qkv.data_ptr() % 16 or kc.data_ptr() % 16 or vc.data_ptr() % 16
+            or length.dtype != torch.int64 or not length.is_cuda):
+        raise ValueError(f"{what}: unsupported layout")
+
+
+def kv_cache_store_fp8(qkv, kc, vc, length, n, heads, head_dim, per_seq=False, k_scale=1.0, v_scale=1.0):
+    """The k and v columns of ``n`` rows per sequence of qkv [N*n, 3*H*hd] (bf16) quantised into the
+    fp8 cache rows ``length[s] + i`` (``length`` device int64 [1], or [N] with ``per_seq``; rows at
+    or past S_max are not written): ``dpc_kv_store_fp8`` (``csrc/append_attn.hip``).  The stored
+    byte is ``kv_quantize_ref``'s."""
+    N, Smax, E = kc.shape[0], kc.shape[1], heads * head_dim
+    if kc.dtype != FP8 or vc.dtype != FP8:
+        raise ValueError("kv_cache_store_fp8: kc and vc must be float8_e4m3fn")
+    if length.numel() != (N if per_seq else 1) or qkv.shape[0] != N * n or qkv.shape[1] < 3 * E:
+        raise ValueError("kv_cache_store_fp8: qkv must hold n rows of 3*H*hd per sequence, length [N] or [1]")
+    _check_fp8("kv_cache_store_fp8", qkv, kc, vc, N, Smax, E, head_dim, length)
+    _lib.call("dpc_kv_store_fp8", _lib.AppendAttnFp8Args(
+        qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), len=length.data_ptr(), ldqkv=qkv.stride(0),
+        N=N, n=n, H=heads, hd=head_dim, Smax=Smax, per_seq=int(bool(per_seq)), nsplit=1,
+        **_kv_scales(k_scale, v_scale, "kv_cache_store_fp8")), qkv.device)
+
+
+def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=False, splits=None,
+                     k_scale=1.0, v_scale=1.0):
     """One new token per sequence against a KV cache: appends its key / value at
     ``length`` (device int64 [1], cached tokens so far) and returns o [N, H*hd].
     ``per_seq``: ``length`` is int64 [N], one per sequence (a ragged batch); a sequence whose
@@ -266,12 +327,32 @@ def decode_attention(qkv, kc, vc, length, heads, head_dim, scale=None, per_seq=F
     ``csrc/decode_split.hip``; any ``S_max``); a plan of one split with ``S_max <= DECODE_MAX_S``
     runs ``dpc_decode_attn`` (``csrc/decode.hip``).  ``splits``: that many splits of the split
     kernel, 1 included (tests, timing); the torch path ignores it.
+
+    An fp8 cache (``kc``, ``vc`` float8_e4m3fn; CUDA bf16 qkv, head_dim 32, 64 or 128) holds
+    ``x / scale`` per tensor (``k_scale``, ``v_scale``): the new row is stored quantised
+    (``kv_quantize_ref``) and takes part as stored, so the result is the softmax over the
+    dequantised cache as it stands after the write.  It always runs the split kernel's fp8 twin
+    (``dpc_decode_attn_split_fp8``), a plan of one split included; there is no torch path.
     """
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     N, E = qkv.shape[0], heads * head_dim
     Smax = kc.shape[1]
     if length.numel() != (N if per_seq else 1):
         raise ValueError("decode_attention: length must be [N] with per_seq, [1] without")
+    if kc.dtype == FP8 or vc.dtype == FP8:
+        _check_fp8("decode_attention", qkv, kc, vc, N, Smax, E, head_dim, length)
+        plan = int(splits) if splits is not None else decode_splits(
+            N, heads, Smax, torch.cuda.get_device_properties(qkv.device).multi_processor_count)
+        if not 1 <= plan <= DECODE_MAX_SPLITS:
+            raise ValueError("decode_attention: unsupported layout")
+        o = torch.empty(N, E, device=qkv.device, dtype=torch.bfloat16)
+        ws = torch.empty(N * heads * plan * (head_dim + 2), device=qkv.device, dtype=torch.float32) if plan > 1 else None
+        _lib.call("dpc_decode_attn_split_fp8", _lib.DecodeSplitFp8Args(
+            qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), o=o.data_ptr(), len=length.data_ptr(),
+            ldqkv=qkv.stride(0), ldo=E, N=N, H=heads, hd=head_dim, Smax=Smax, scale=scale,
+            per_seq=int(bool(per_seq)), ws=_lib.ptr(ws), nsplit=plan,
+            **_kv_scales(k_scale, v_scale, "decode_attention")), qkv.device)
+        return o
     if not (qkv.is_cuda and qkv.dtype == torch.bfloat16):
         if per_seq:
             o = torch.zeros(N, E, device=qkv.device, dtype=qkv.dtype)
@@ -357,7 +438,8 @@ def _append_torch(qkv, kc, vc, start, n, heads, head_dim, scale):
     return o.reshape(N * n, E)
 
 
-def append_attention(qkv, kc, vc, length, n, heads, head_dim, scale=None, per_seq=False, splits=None):
+def append_attention(qkv, kc, vc, length, n, heads, head_dim, scale=None, per_seq=False, splits=None,
+                     k_scale=1.0, v_scale=1.0):
     """A block of ``n`` new tokens per sequence against a KV cache that may already hold tokens:
     token i of sequence s sits at position p = length[s] + i (``length`` device int64 [1], or [N]
     with ``per_seq``); its key / value go to cache row p and its output row is the softmax over
@@ -368,7 +450,11 @@ def append_attention(qkv, kc, vc, length, n, heads, head_dim, scale=None, per_se
     or 128): ``dpc_append_attn`` (``csrc/append_attn.hip``), the length read on the device so that
     the call can be graph-captured; ``append_splits`` workgroups share the keys of a query tile,
     their partials combined by a further launch.  ``splits``: that many, 1 included (tests, timing).
-    Anything else runs the materialised torch path, which reads the length on the host."""
+    Anything else runs the materialised torch path, which reads the length on the host.
+
+    An fp8 cache (float8_e4m3fn, ``k_scale`` / ``v_scale`` as in ``decode_attention``): the block's
+    rows are stored quantised first (``dpc_append_attn_fp8``) and every key, the block's own
+    included, is read back from the cache; HIP only."""
     scale = 1.0 / math.sqrt(head_dim) if scale is None else scale
     N, Smax, E = kc.shape[0], kc.shape[1], heads * head_dim
     if length.numel() != (N if per_seq else 1):
@@ -377,6 +463,9 @@ def append_attention(qkv, kc, vc, length, n, heads, head_dim, scale=None, per_se
         raise ValueError("append_attention: qkv must hold n rows of 3*H*hd per sequence")
     if not scale > 0:  # the kernel takes the tile maximum on raw scores and scales it afterwards
         raise ValueError("append_attention: scale must be positive")
+    fp8 = kc.dtype == FP8 or vc.dtype == FP8
+    if fp8:
+        _check_fp8("append_attention", qkv, kc, vc, N, Smax, E, head_dim, length)
     if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and head_dim in HD_KERNELS):
         if not per_seq:
             return _append_torch(qkv, kc, vc, int(length), n, heads, head_dim, scale)
@@ -388,15 +477,19 @@ def append_attention(qkv, kc, vc, length, n, heads, head_dim, scale=None, per_se
     else:
         plan = int(splits)
     if (qkv.stride(1) != 1 or kc.shape != (N, Smax, E) or vc.shape != kc.shape
-            or not kc.is_contiguous() or not vc.is_contiguous() or kc.dtype != torch.bfloat16
-            or vc.dtype != torch.bfloat16 or not 1 <= plan <= APPEND_MAX_SPLITS or N * heads > 65535
+            or not kc.is_contiguous() or not vc.is_contiguous() or kc.dtype != (FP8 if fp8 else torch.bfloat16)
+            or vc.dtype != kc.dtype or not 1 <= plan <= APPEND_MAX_SPLITS or N * heads > 65535
             or qkv.stride(0) % 8 or qkv.data_ptr() % 16 or length.dtype != torch.int64 or not length.is_cuda):
         raise ValueError("append_attention: unsupported layout")
     o = torch.empty(N * n, E, device=qkv.device, dtype=torch.bfloat16)
     # the partials live like o: allocated per call, so a capture keeps them in the graph's pool
     ws = torch.empty(N * n * heads * plan * (head_dim + 4), device=qkv.device, dtype=torch.float32) if plan > 1 else None
-    _lib.call("dpc_append_attn", _lib.AppendAttnArgs(
-        qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), o=o.data_ptr(), len=length.data_ptr(),
-        ldqkv=qkv.stride(0), ldo=E, N=N, n=n, H=heads, hd=head_dim, Smax=Smax, scale=scale,
-        per_seq=int(bool(per_seq)), ws=_lib.ptr(ws), nsplit=plan), qkv.device)
+    common = dict(qkv=qkv.data_ptr(), kc=kc.data_ptr(), vc=vc.data_ptr(), o=o.data_ptr(), len=length.data_ptr(),
+                  ldqkv=qkv.stride(0), ldo=E, N=N, n=n, H=heads, hd=head_dim, Smax=Smax, scale=scale,
+                  per_seq=int(bool(per_seq)), ws=_lib.ptr(ws), nsplit=plan)
+    if fp8:
+        _lib.call("dpc_append_attn_fp8", _lib.AppendAttnFp8Args(
+            **common, **_kv_scales(k_scale, v_scale, "append_attention")), qkv.device)
+    else:
+        _lib.call("dpc_append_attn", _lib.AppendAttnArgs(**common), qkv.device)
     return o

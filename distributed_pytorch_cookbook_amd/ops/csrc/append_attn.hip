@@ -36,7 +36,22 @@
 //   append_attn_combine_kernel   (nsplit > 1) one thread per (row, head dim): the partials in index
 //                         order, an empty split has l = 0.  No float atomics anywhere: the same
 //                         inputs give the same bits on every run.
-#include "common.h"
+//
+// The 1-byte e4m3 cache (fp8.h; dpc_append_attn_fp8) differs in the first launch and in the
+// staging alone:
+//   kv_store_fp8_kernel   in place of append_kv_kernel: a thread takes 16 output bytes -- two 16-B
+//                         bf16 loads, x inv_scale, clamp, eight converts, one 16-B store.
+//   append_attn_kernel<HD, fp8_t>   fetch loads 8 bytes (8 elements) where the bf16 path loads 16,
+//                         with the same thread-to-chunk assignment, and stage widens them to 8
+//                         bf16 (exact: the upper halves of the converted f32) into the same 16-B
+//                         LDS chunk.  The LDS image, the MFMA loop, masking, splits and combine
+//                         are shared; k_scale multiplies c, v_scale multiplies o once on its way
+//                         out (normalised output or partial).  The block's own keys are read back
+//                         from the cache like every other key: quantised first, then attended to.
+//                         (16-B loads with another assignment were not tried: unmeasured.)
+#include "fp8.h"
+
+#include <type_traits>
 
 namespace dpc {
 
@@ -134,9 +149,53 @@ __global__ __launch_bounds__(ANT) void append_kv_kernel(AppendAttnArgs p) {
   reinterpret_cast<uint4*>(dst)[cc] = reinterpret_cast<const uint4*>(src)[cc];
 }
 
+struct AppendAttnFp8Args {  // AppendAttnArgs (kc / vc e4m3) + the cache's scales
+  const void* qkv;
+  void* kc;
+  void* vc;
+  void* o;
+  const long long* len;
+  long long ldqkv, ldo;
+  int N, n, H, hd, Smax;
+  float scale;
+  int per_seq;
+  float* ws;
+  int nsplit;
+  float k_scale, k_inv, v_scale, v_inv;
+};
+
+static AppendAttnArgs ap_plain(const AppendAttnFp8Args& f) {
+  AppendAttnArgs a;
+  a.qkv = f.qkv, a.kc = f.kc, a.vc = f.vc, a.o = f.o, a.len = f.len;
+  a.ldqkv = f.ldqkv, a.ldo = f.ldo;
+  a.N = f.N, a.n = f.n, a.H = f.H, a.hd = f.hd, a.Smax = f.Smax;
+  a.scale = f.scale, a.per_seq = f.per_seq, a.ws = f.ws, a.nsplit = f.nsplit;
+  return a;
+}
+
+// thread g: 16-element chunk g % (2 E / 16) of token g / (2 E / 16)'s k | v columns, quantised
+__global__ __launch_bounds__(ANT) void kv_store_fp8_kernel(AppendAttnArgs p, float k_inv, float v_inv) {
+  const int E = p.H * p.hd, cpt = E >> 3;  // chunks per token: k and v
+  const long long g = (long long)blockIdx.x * ANT + threadIdx.x;
+  const long long tok = g / cpt;
+  if (tok >= (long long)p.N * p.n) return;
+  const int c = (int)(g - tok * cpt);
+  const int s = (int)(tok / p.n), i = (int)(tok - (long long)s * p.n);
+  const int start = ap_start(p, s);
+  if (start < 0 || i >= p.Smax - start) return;  // position start + i past the capacity: not written
+  const bool isk = c < (E >> 4);
+  const int cc = isk ? c : c - (E >> 4);
+  const uint4* src = reinterpret_cast<const uint4*>(static_cast<const bf16_t*>(p.qkv) + tok * p.ldqkv + (isk ? E : 2 * E)) + 2 * cc;
+  fp8_t* dst = static_cast<fp8_t*>(isk ? p.kc : p.vc) + ((long long)s * p.Smax + start + i) * E;
+  reinterpret_cast<uint4*>(dst)[cc] = fp8_quant16(src[0], src[1], isk ? k_inv : v_inv);
+}
+
 // ------------------------------------------------------------------ attention
-template <int HD>
-__global__ __launch_bounds__(ANT) void append_attn_kernel(AppendAttnArgs p) {
+// CT: the cache element, bf16_t or fp8_t; ks / vs: the e4m3 cache's scales (unused for bf16)
+template <int HD, typename CT = bf16_t>
+__global__ __launch_bounds__(ANT) void append_attn_kernel(AppendAttnArgs p, float ks, float vs) {
+  constexpr bool FP8 = std::is_same<CT, fp8_t>::value;
+  typedef typename std::conditional<FP8, uint2, uint4>::type ld_t;  // a chunk of 8 cache elements
   constexpr int TILE = AKT * HD;    // elements of one tile
   constexpr int NST = HD / 16;      // k-steps of a product over the head
   constexpr int NDT = HD / 32;      // 32-column blocks of the O accumulator
@@ -175,22 +234,22 @@ __global__ __launch_bounds__(ANT) void append_attn_kernel(AppendAttnArgs p) {
     for (int st = 0; st < NST; ++st)
       qf[st] = qvalid ? *reinterpret_cast<const bf16x8*>(Q + 16 * st + 8 * hh) : bf16x8{};
   }
-  const float c = p.scale * ALOG2E;
+  const float c = FP8 ? p.scale * ALOG2E * ks : p.scale * ALOG2E;  // (e4m3: K dequantised here)
 
-  const bf16_t* K = static_cast<const bf16_t*>(p.kc) + (long long)s * Smax * E + h * HD;
-  const bf16_t* V = static_cast<const bf16_t*>(p.vc) + (long long)s * Smax * E + h * HD;
+  const CT* K = static_cast<const CT*>(p.kc) + (long long)s * Smax * E + h * HD;
+  const CT* V = static_cast<const CT*>(p.vc) + (long long)s * Smax * E + h * HD;
   // thread's chunk i of a tile: key row (tid + ANT i) / CPR, chunk (tid + ANT i) % CPR
-  uint4 kr[NLD], vr[NLD];
+  ld_t kr[NLD], vr[NLD];
   auto fetch = [&](int t) {  // rows at or past kend land as zeros (never read past the live keys)
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int g = tid + ANT * i, row = g / CPR, ch = g % CPR;
       const int j = t * AKT + row;
-      kr[i] = make_uint4(0u, 0u, 0u, 0u);
-      vr[i] = make_uint4(0u, 0u, 0u, 0u);
+      kr[i] = ld_t{};
+      vr[i] = ld_t{};
       if (j < kend) {
-        kr[i] = reinterpret_cast<const uint4*>(K + (long long)j * E)[ch];
-        vr[i] = reinterpret_cast<const uint4*>(V + (long long)j * E)[ch];
+        kr[i] = reinterpret_cast<const ld_t*>(K + (long long)j * E)[ch];
+        vr[i] = reinterpret_cast<const ld_t*>(V + (long long)j * E)[ch];
       }
     }
   };
@@ -199,8 +258,15 @@ __global__ __launch_bounds__(ANT) void append_attn_kernel(AppendAttnArgs p) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int g = tid + ANT * i, off = ap_toff<HD>(g / CPR, g % CPR);
-      *reinterpret_cast<uint4*>(buf + off) = kr[i];
-      *reinterpret_cast<uint4*>(buf + TILE + off) = vr[i];
+      if constexpr (FP8) {  // 8 e4m3 -> 8 bf16, exact
+        const uint2 k0 = fp8_to_bf16x4(kr[i].x), k1 = fp8_to_bf16x4(kr[i].y);
+        const uint2 v0 = fp8_to_bf16x4(vr[i].x), v1 = fp8_to_bf16x4(vr[i].y);
+        *reinterpret_cast<uint4*>(buf + off) = make_uint4(k0.x, k0.y, k1.x, k1.y);
+        *reinterpret_cast<uint4*>(buf + TILE + off) = make_uint4(v0.x, v0.y, v1.x, v1.y);
+      } else {
+        *reinterpret_cast<uint4*>(buf + off) = kr[i];
+        *reinterpret_cast<uint4*>(buf + TILE + off) = vr[i];
+      }
     }
   };
 
@@ -291,7 +357,7 @@ __global__ __launch_bounds__(ANT) void append_attn_kernel(AppendAttnArgs p) {
   if (qi >= n) return;
   // lane (query lane & 31, half hh) holds head dims 32 d + 8 g + 4 hh .. + 3 in o[d][4 g .. 4 g + 3]
   if (p.nsplit == 1) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    const float inv = l > 0.f ? (FP8 ? vs : 1.f) / l : 0.f;  // (e4m3: V dequantised here)
     bf16_t* O = static_cast<bf16_t*>(p.o) + tok * p.ldo + h * HD;
 #pragma unroll
     for (int d = 0; d < NDT; ++d)
@@ -305,6 +371,12 @@ __global__ __launch_bounds__(ANT) void append_attn_kernel(AppendAttnArgs p) {
     return;
   }
   float* wsp = p.ws + ((tok * p.H + h) * p.nsplit + sp) * (HD + 4);
+  if constexpr (FP8) {
+#pragma unroll
+    for (int d = 0; d < NDT; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[d][r] *= vs;
+  }
 #pragma unroll
   for (int d = 0; d < NDT; ++d)
 #pragma unroll
@@ -339,10 +411,30 @@ __global__ __launch_bounds__(ANT) void append_attn_combine_kernel(AppendAttnArgs
   static_cast<bf16_t*>(p.o)[tok * p.ldo + h * hd + t] = f2bf(den > 0.f ? num / den : 0.f);
 }
 
-template <int HD>
-static void append_attn_launch(const AppendAttnArgs* a, hipStream_t stream) {
+template <int HD, typename CT = bf16_t>
+static void append_attn_launch(const AppendAttnArgs* a, hipStream_t stream, float ks = 1.f, float vs = 1.f) {
   const dim3 grid((unsigned)((a->n + AQB - 1) / AQB), (unsigned)a->nsplit, (unsigned)(a->N * a->H));
-  hipLaunchKernelGGL(append_attn_kernel<HD>, grid, dim3(ANT), 0, stream, *a);
+  hipLaunchKernelGGL((append_attn_kernel<HD, CT>), grid, dim3(ANT), 0, stream, *a, ks, vs);
+}
+
+static bool ap_bad(const AppendAttnArgs* a) {
+  return (a->hd != 32 && a->hd != 64 && a->hd != 128) || a->ldqkv % 8 || a->ldo % 8 || a->H <= 0 || a->Smax <= 0 ||
+         !(a->scale > 0.f) || a->Smax > (1 << 30) || a->n > (1 << 22) || (long long)a->N * a->H > 65535 || a->nsplit < 1 ||
+         a->nsplit > APPEND_MAX_SPLITS || (a->nsplit > 1 && !a->ws) || ((uintptr_t)a->qkv % 16) ||
+         ((uintptr_t)a->kc % 16) || ((uintptr_t)a->vc % 16) || ((uintptr_t)a->o % 16) || ((uintptr_t)a->ws % 16);
+}
+
+static int ap_combine(const AppendAttnArgs* a, hipStream_t stream) {
+  const long long rows = (long long)a->N * a->n * a->H;
+  const int rpb = ANT / a->hd;
+  hipLaunchKernelGGL(append_attn_combine_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(ANT), 0, stream, *a);
+  return (int)hipGetLastError();
+}
+
+static int kv_store_fp8(const AppendAttnArgs* a, float k_inv, float v_inv, hipStream_t stream) {
+  const long long chunks = (long long)a->N * a->n * (a->H * a->hd / 8);
+  hipLaunchKernelGGL(kv_store_fp8_kernel, dim3((unsigned)((chunks + ANT - 1) / ANT)), dim3(ANT), 0, stream, *a, k_inv, v_inv);
+  return (int)hipGetLastError();
 }
 
 }  // namespace dpc
@@ -362,11 +454,7 @@ DPC_API void dpc_append_attn_tiles(int hd, int* qb, int* kt) {
 // rows 16-B aligned; ws (nsplit > 1) holds N*n*H*nsplit*(hd + 4) floats.
 DPC_API int dpc_append_attn(const AppendAttnArgs* a, hipStream_t stream) {
   if (a->N <= 0 || a->n <= 0) return 0;
-  if ((a->hd != 32 && a->hd != 64 && a->hd != 128) || a->ldqkv % 8 || a->ldo % 8 || a->H <= 0 || a->Smax <= 0 ||
-      !(a->scale > 0.f) || a->Smax > (1 << 30) || a->n > (1 << 22) || (long long)a->N * a->H > 65535 || a->nsplit < 1 ||
-      a->nsplit > APPEND_MAX_SPLITS || (a->nsplit > 1 && !a->ws) || ((uintptr_t)a->qkv % 16) ||
-      ((uintptr_t)a->kc % 16) || ((uintptr_t)a->vc % 16) || ((uintptr_t)a->o % 16) || ((uintptr_t)a->ws % 16))
-    return (int)hipErrorInvalidValue;
+  if (ap_bad(a)) return (int)hipErrorInvalidValue;
   const long long chunks = (long long)a->N * a->n * (a->H * a->hd / 4);
   hipLaunchKernelGGL(append_kv_kernel, dim3((unsigned)((chunks + ANT - 1) / ANT)), dim3(ANT), 0, stream, *a);
   int rc = (int)hipGetLastError();
@@ -378,8 +466,36 @@ DPC_API int dpc_append_attn(const AppendAttnArgs* a, hipStream_t stream) {
   }
   rc = (int)hipGetLastError();
   if (rc || a->nsplit == 1) return rc;
-  const long long rows = (long long)a->N * a->n * a->H;
-  const int rpb = ANT / a->hd;
-  hipLaunchKernelGGL(append_attn_combine_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(ANT), 0, stream, *a);
-  return (int)hipGetLastError();
+  return ap_combine(a, stream);
+}
+
+// The quantising store alone: n rows per sequence of qkv's k and v columns into the e4m3 cache at
+// rows len[s] + i (those below Smax).  Reads qkv, kc, vc, len, ldqkv, N, n, H, hd, Smax, per_seq and
+// the inverse scales; hd 32, 64 or 128.
+DPC_API int dpc_kv_store_fp8(const AppendAttnFp8Args* f, hipStream_t stream) {
+  if (f->N <= 0 || f->n <= 0) return 0;
+  if ((f->hd != 32 && f->hd != 64 && f->hd != 128) || f->ldqkv % 8 || f->H <= 0 || f->Smax <= 0 || f->Smax > (1 << 30) ||
+      f->n > (1 << 22) || !(f->k_inv > 0.f) || !(f->v_inv > 0.f) || ((uintptr_t)f->qkv % 16) ||
+      ((uintptr_t)f->kc % 16) || ((uintptr_t)f->vc % 16))
+    return (int)hipErrorInvalidValue;
+  const AppendAttnArgs a = ap_plain(*f);
+  return kv_store_fp8(&a, f->k_inv, f->v_inv, stream);
+}
+
+// dpc_append_attn over an e4m3 cache: the same requirements, and positive scales.
+DPC_API int dpc_append_attn_fp8(const AppendAttnFp8Args* f, hipStream_t stream) {
+  if (f->N <= 0 || f->n <= 0) return 0;
+  const AppendAttnArgs a = ap_plain(*f);
+  if (ap_bad(&a) || !(f->k_scale > 0.f) || !(f->v_scale > 0.f) || !(f->k_inv > 0.f) || !(f->v_inv > 0.f))
+    return (int)hipErrorInvalidValue;
+  int rc = kv_store_fp8(&a, f->k_inv, f->v_inv, stream);
+  if (rc) return rc;
+  switch (a.hd) {
+    case 32: append_attn_launch<32, fp8_t>(&a, stream, f->k_scale, f->v_scale); break;
+    case 64: append_attn_launch<64, fp8_t>(&a, stream, f->k_scale, f->v_scale); break;
+    default: append_attn_launch<128, fp8_t>(&a, stream, f->k_scale, f->v_scale); break;
+  }
+  rc = (int)hipGetLastError();
+  if (rc || a.nsplit == 1) return rc;
+  return ap_combine(&a, stream);
 }

@@ -49,27 +49,34 @@ def prepare_batch(batch, pad_id: int, device):
 @torch.inference_mode()
 def generate(model, prompt: str, tokenizer, device, max_new_tokens: int = 20, use_cache: bool = True,
              temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-             prefill_chunk: int = 0) -> str:
+             prefill_chunk: int = 0, kv_dtype=None) -> str:
     """``prefill_chunk``: the KV-cache decode takes a prompt longer than that in blocks of that many
-    tokens (0: in one)."""
+    tokens (0: in one).  ``kv_dtype``: "fp8" for the 1-byte KV cache (``new_kv_cache``); a model
+    without ``decode`` ignores it, as it ignores the cache."""
     if temperature > 0 or top_k > 0 or top_p < 1.0:  # sampling: the batched loop with one prompt
         return generate_batch(model, [prompt], tokenizer, device, max_new_tokens, temperature, top_k, top_p, seed,
-                              prefill_chunk)[0]
+                              prefill_chunk, kv_dtype)[0]
     batch = tokenizer([prompt], truncation=True, max_length=256, return_tensors="pt")
     input_ids = batch["input_ids"].to(device)
     # the learned position table bounds the context: slide a window past it
     max_pos = getattr(model, "max_position_embeddings", None) or 1 << 30
     if use_cache and hasattr(model, "decode") and input_ids.shape[1] + max_new_tokens <= max_pos:
-        return _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk)
+        return _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk, kv_dtype)
     new = _recompute(model, input_ids, device, max_new_tokens, max_pos, tokenizer.eos_token_id,
                      lambda logits, i: int(logits.argmax(dim=-1)))
     return tokenizer.decode(input_ids[0].tolist() + new, skip_special_tokens=True)
 
 
-def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk=0):
+def _kv_kw(kv_dtype):
+    """``new_kv_cache``'s keyword for a cache dtype (none for the default: a model's own
+    ``new_kv_cache`` need not know the keyword)."""
+    return {} if kv_dtype in (None, "bf16") else {"kv_dtype": kv_dtype}
+
+
+def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk=0, kv_dtype=None):
     """KV-cache greedy decode: one prefill of the prompt, then one token per forward (same
     tokens as the full-recompute loop while the context fits the position table)."""
-    cache = model.new_kv_cache(1, input_ids.shape[1] + max_new_tokens)
+    cache = model.new_kv_cache(1, input_ids.shape[1] + max_new_tokens, **_kv_kw(kv_dtype))
     s = input_ids.shape[1]
     logits = model.decode(input_ids, torch.arange(s, device=device).unsqueeze(0), cache, prefill_chunk=prefill_chunk)
     out = input_ids[0].tolist()
@@ -125,11 +132,12 @@ DONE_POLL = 8  # steps between two reads of the done flags
 
 @torch.inference_mode()
 def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, temperature: float = 0.0,
-                   top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0) -> list:
+                   top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None) -> list:
     """Continuations of ``prompts`` (a list of strings), sampled with ``temperature`` / ``top_k`` /
     ``top_p`` from the counter-based stream of ``seed`` (row n of the batch draws
     ``sample_uniform(seed, n, step)``: the same arguments give the same text, on every rank).
-    ``prefill_chunk``: the padded prompts go into the cache in blocks of that many tokens (0: in one)."""
+    ``prefill_chunk``: the padded prompts go into the cache in blocks of that many tokens (0: in one).
+    ``kv_dtype``: "fp8" for the 1-byte KV cache (ignored without ``decode``)."""
     from ..ops.sample import Sampler
 
     device = torch.device(device)
@@ -143,7 +151,7 @@ def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, 
     max_pos = getattr(model, "max_position_embeddings", None) or 1 << 30
     sampler = Sampler(N, max_new_tokens, device, temperature, top_k, top_p, seed, eos)
     if hasattr(model, "decode") and max(lens) + max_new_tokens <= max_pos:
-        _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk)
+        _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk, kv_dtype)
         new = sampler.sequences()
     else:
         new = [_recompute(model, t.view(1, -1).to(device), device, max_new_tokens, max_pos, eos,
@@ -151,14 +159,14 @@ def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, 
     return [tokenizer.decode(t.tolist() + g, skip_special_tokens=True) for t, g in zip(ids, new)]
 
 
-def _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk=0):
+def _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk=0, kv_dtype=None):
     """One prefill of the right-padded prompts into a ragged KV cache, then one token per sequence
     per step: a replayed HIP graph ending in the sampler where the model has one, else eagerly."""
     N, S = len(ids), max(lens)
     padded = torch.zeros(N, S, dtype=torch.int64)
     for n, t in enumerate(ids):
         padded[n, :lens[n]] = t
-    cache = model.new_kv_cache(N, S + max_new_tokens, ragged=True)
+    cache = model.new_kv_cache(N, S + max_new_tokens, ragged=True, **_kv_kw(kv_dtype))
     logits = model.decode(padded.to(device), None, cache, lens=lens, prefill_chunk=prefill_chunk)
     sampler(logits[:, 0])  # (the prefill has set the lengths: token 0 goes to position lens[n])
     dec = None
