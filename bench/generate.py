@@ -7,11 +7,13 @@ ms per step, and ms per token per sequence = that / B).
 
     python bench/generate.py [--model gpt2-small] [--ctx 1000] [--tokens 20]
                              [--batch 8 --temperature 0.8 --top_k 50 --top_p 0.9]
-                             [--prefill_chunk 512] [--kv_dtype fp8]
+                             [--prefill_chunk 512] [--kv_dtype fp8] [--weight_dtype fp8]
 
 ``prefill_ms``: the prompt into an empty cache (the median of three, after a warm-up prefill), in
 blocks of ``--prefill_chunk`` tokens where given (every prefill of the KV-cache sections then runs
 in blocks, the eager ``kv_cache`` one included); the position table grows with ``--ctx``.
+``--weight_dtype fp8``: the one-token steps of the KV-cache sections run on an e4m3 copy of the
+Linear weights (``quantize_decode_weights``; ``quantize_ms``: the one-time cost of making it).
 """
 import argparse
 import json
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--prefill_chunk", type=int, default=0, help="prefill in blocks of this many tokens (0: in one)")
     ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"], help="element of the KV cache")
+    ap.add_argument("--weight_dtype", default="bf16", choices=["bf16", "fp8"], help="weights of the one-token steps")
     a = ap.parse_args()
     kv = {"kv_dtype": a.kv_dtype}
     p = PRESETS[a.model]
@@ -47,6 +50,16 @@ def main():
                                  max(1024, a.ctx + a.tokens + 4), activation=p["activation"])
     m.eval()
     res = {}
+    wkw = {}
+    if a.weight_dtype == "fp8":
+        from distributed_pytorch_cookbook_amd.models.decode import quantize_decode_weights
+
+        quantize_decode_weights(m)  # (warm-up: library load, allocator)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        wkw = {"weights": quantize_decode_weights(m)}
+        torch.cuda.synchronize()
+        res["quantize_ms"] = (time.perf_counter() - t0) * 1e3
     for last_only in (() if a.graph_only else (False, True)):
         ids = torch.randint(0, 50257, (1, a.ctx), device=dev)
         with torch.inference_mode():
@@ -70,7 +83,7 @@ def main():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
             nxt = logits[0, -1].argmax().view(1, 1)
-            logits = m.decode(nxt, torch.full((1, 1), cache.len, device=dev), cache)
+            logits = m.decode(nxt, torch.full((1, 1), cache.len, device=dev), cache, **wkw)
         torch.cuda.synchronize()
     if not a.graph_only:
         res["kv_cache"] = (time.perf_counter() - t0) / a.tokens * 1e3
@@ -85,7 +98,7 @@ def main():
             torch.cuda.synchronize()
             prefill.append((time.perf_counter() - t0) * 1e3)
         res["prefill_ms"] = sorted(prefill)[1]
-        dec = m.graph_decoder(cache)
+        dec = m.graph_decoder(cache, **wkw)
         for i in range(a.tokens + 3):
             if i == 3:
                 torch.cuda.synchronize()
@@ -105,7 +118,7 @@ def main():
             cache = m.new_kv_cache(B, a.ctx + a.tokens + 4, ragged=True, **kv)
             sampler = Sampler(B, a.tokens + 4, dev, a.temperature, a.top_k, a.top_p, seed=0, eos=-1)
             sampler(m.decode(ids, None, cache, lens=lens)[:, 0])
-            dec = m.graph_decoder(cache, sampler)
+            dec = m.graph_decoder(cache, sampler, **wkw)
             for i in range(a.tokens + 3):
                 if i == 3:
                     torch.cuda.synchronize()
@@ -116,7 +129,8 @@ def main():
         batched = {"batch": B, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
                    "ms_per_step": ms, "ms_per_token_per_sequence": ms / B}
         res["kv_cache_graph_batched"] = ms
-    head = {"model": a.model, "ctx": a.ctx, "prefill_chunk": a.prefill_chunk, "kv_dtype": a.kv_dtype}
+    head = {"model": a.model, "ctx": a.ctx, "prefill_chunk": a.prefill_chunk, "kv_dtype": a.kv_dtype,
+            "weight_dtype": a.weight_dtype}
     if a.graph_only:
         print(json.dumps({**head, "ms_per_token": res, "kv_cache_graph_batched": batched}))
         return

@@ -1,4 +1,4 @@
-"""One Linear of 16..64 rows alone, at the shapes of a GPT-2 small / GPT-2 XL decode step (QKV, the
+"""One Linear of 1..64 rows alone, at the shapes of a GPT-2 small / GPT-2 XL decode step (QKV, the
 out-projection with bias and f32 residual, the up-projection with bias and GELU, the
 down-projection with bias and f32 residual, the LM head over the padded vocabulary): the skinny
 kernel (``dpc_gemm_skinny``, csrc/skinny_gemm.hip) with the planner's plan -- and with every
@@ -12,7 +12,12 @@ Infinity Cache): a weight that stayed in cache would flatter every variant.  Bes
 weight bytes the product must read and those bytes over the time.  One JSON line per
 (shape, rows, variant).
 
-    python bench/skinny_time.py [--rows 16 17 32 48 64] [--models gpt2-small gpt2-xl] [--plans]
+``--weight_dtype fp8``: beside what bf16 weights run at that row count, the fp8-weight kernel
+(``dpc_gemm_wq8``, csrc/wq_gemm.hip) on a quantised copy of every weight copy, under both plans;
+its weight bytes are half.
+
+    python bench/skinny_time.py [--rows 1 8 16 17 32 48 64] [--models gpt2-small gpt2-xl] [--plans]
+                                [--weight_dtype fp8]
 """
 import argparse
 import json
@@ -38,9 +43,10 @@ def shapes(D):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", type=int, nargs="+", default=[16, 17, 32, 48, 64])
+    ap.add_argument("--rows", type=int, nargs="+", default=[1, 8, 16, 17, 32, 48, 64])
     ap.add_argument("--models", nargs="+", default=list(DIMS))
     ap.add_argument("--plans", action="store_true", help="also every instantiated (columns, waves) plan")
+    ap.add_argument("--weight_dtype", default="bf16", choices=["bf16", "fp8"], help="fp8: also dpc_gemm_wq8")
     ap.add_argument("--cache_mb", type=int, default=768, help="weight copies cover at least this much")
     ap.add_argument("--min_calls", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=5)
@@ -65,6 +71,7 @@ def main():
             w_bytes = Nw * K * 2
             copies = max(a.min_calls, -(-a.cache_mb * 2**20 // w_bytes))
             ws = [(torch.randn(Nw, K, device=dev) / K ** 0.5).bfloat16() for _ in range(copies)]
+            qs = [G.quantize_weight(w) for w in ws] if a.weight_dtype == "fp8" else None
             bias = torch.randn(Nw, device=dev) if has_bias else None
             for M in a.rows:
                 x = torch.randn(M, K, device=dev).bfloat16()
@@ -78,23 +85,29 @@ def main():
                 for pl in ((plan,) + tuple(p for p in G.SKINNY_PLANS if a.plans and p != plan)):
                     variants.append((f"skinny {pl[0]}x{pl[1]}" + (" (plan)" if pl == plan else ""),
                                      lambda w, pl=pl: G._linear_fwd_skinny(x, w, bias, act, res, out, odt, plan=pl)))
+                variants = [(vname, fn, ws, w_bytes) for vname, fn in variants]
+                if qs is not None:
+                    for pl in G.SKINNY_PLANS:
+                        variants.append((f"fp8 {pl[0]}x{pl[1]}" + (" (plan)" if pl == plan else ""),
+                                         lambda w, pl=pl: G._linear_fwd_wq8(x, w, bias, act, res, out, odt, plan=pl),
+                                         qs, w_bytes // 2))
                 ref = None
-                for vname, fn in variants:
-                    o = fn(ws[0]).float().clone()
+                for vname, fn, weights, nbytes in variants:
+                    o = fn(weights[0]).float().clone()
                     ref = o if ref is None else ref
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
-                        for w in ws:
+                        for w in weights:
                             fn(w)
                     timed(g, copies)
                     us = [timed(g, copies) for _ in range(a.rounds)]
                     med = statistics.median(us)
                     print(json.dumps({"model": model, "shape": name, "N": N, "K": K, "rows": M, "variant": vname,
                                       "us_per_call": round(med, 2), "min_us": round(min(us), 2),
-                                      "max_us": round(max(us), 2), "weight_bytes": w_bytes,
-                                      "weight_bytes_per_s": round(w_bytes / (med * 1e-6)),
+                                      "max_us": round(max(us), 2), "weight_bytes": nbytes,
+                                      "weight_bytes_per_s": round(nbytes / (med * 1e-6)),
                                       "max_diff_vs_first": round((o - ref).abs().max().item(), 5)}), flush=True)
-            del ws
+            del ws, qs
 
 
 if __name__ == "__main__":

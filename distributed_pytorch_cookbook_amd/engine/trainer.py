@@ -336,18 +336,20 @@ class Trainer:
             return
         a = self.args
         kv_dtype = getattr(a, "kv_cache_dtype", "bf16")
+        weight_dtype = getattr(a, "decode_weight_dtype", "bf16")
         if getattr(a, "temperature", 0.0) > 0:
             if self.log:
                 print(f"Sampling from model (temperature={a.temperature}, top_k={a.top_k}, top_p={a.top_p})")
             for s in generate_batch(e.lm(), list(PROMPTS), self.tok, self.device, temperature=a.temperature,
-                                    top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed, kv_dtype=kv_dtype):
+                                    top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed, kv_dtype=kv_dtype,
+                                    weight_dtype=weight_dtype):
                 if self.log:
                     print(s)
             return
         if self.log:
             print("Argmax sampling from model")
         for p in PROMPTS:
-            s = generate(e.lm(), p, self.tok, self.device, kv_dtype=kv_dtype)
+            s = generate(e.lm(), p, self.tok, self.device, kv_dtype=kv_dtype, weight_dtype=weight_dtype)
             if self.log:
                 print(s)
 

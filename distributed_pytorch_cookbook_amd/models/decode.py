@@ -13,8 +13,8 @@ import math
 import torch
 
 from ..ops.attention import FP8, append_attention, attention_fwd, decode_attention, kv_cache_store_fp8
-from ..ops.gemm import act_code
-from .fused import _layer_forward, ensure_store, head_logits, last_rows, run_embeddings
+from ..ops.gemm import _SKINNY_MAX_ROWS, act_code, quantize_weight
+from .fused import _layer_forward, _qkv_weight, ensure_store, head_logits, last_rows, run_embeddings
 
 
 class KVCache:
@@ -81,6 +81,54 @@ class KVCache:
     def positions(self, N: int) -> torch.Tensor:
         """Position ids [N, 1] of the next token, read from the device lengths."""
         return self.len_t.view(N, 1) if self.ragged else self.len_t.expand(N, 1)
+
+
+class Fp8DecodeStore:
+    """The model's parameter store with an fp8 (e4m3, one f32 scale per output row) copy of the
+    Linear weights a one-token step streams: each layer's fused QKV, ``to_out``, ``up_proj`` and
+    ``down_proj`` and the LM head, as ``ops/gemm.py:QWeight`` -- ``linear_fwd`` then runs
+    ``dpc_gemm_wq8`` (csrc/wq_gemm.hip).  LayerNorm weights, biases and embeddings are the wrapped
+    store's, as is everything else.  The copy is extra memory beside the bf16 weights (prefill and
+    blocks of tokens keep those: about 1.6 GB for GPT-2 XL), and a snapshot: it does not follow
+    later updates of the weights."""
+
+    def __init__(self, model, store):
+        self._store = store
+        self._q, self._qkv = {}, {}
+        for layer in model.decoder.layers:
+            self._qkv[id(layer.attn)] = quantize_weight(_qkv_weight(store, layer.attn))
+            for lin in (layer.attn.to_out, layer.fc.up_proj, layer.fc.down_proj):
+                self._q[id(lin.weight)] = quantize_weight(store.weight(lin.weight))
+        self._q[id(model.lm_head.weight)] = quantize_weight(store.weight(model.lm_head.weight))
+
+    def weight(self, p):
+        q = self._q.get(id(p))
+        return q if q is not None else self._store.weight(p)
+
+    def qkv_weight(self, attn):
+        return self._qkv[id(attn)]
+
+    def __getattr__(self, name):
+        return getattr(self._store, name)
+
+
+def quantize_decode_weights(model) -> Fp8DecodeStore:
+    """An ``Fp8DecodeStore`` of the model's weights as they are now, for ``decode_step`` /
+    ``GraphDecoder`` / ``model.decode(..., weights=)``.  Needs CUDA and a bf16 non-sharded store
+    (``ValueError`` otherwise); the step takes at most 64 sequences."""
+    from ..parallel.store import LocalStore
+
+    store = ensure_store(model)
+    device = next(model.parameters()).device
+    if device.type != "cuda" or not isinstance(store, LocalStore) or store.compute_dtype != torch.bfloat16:
+        raise ValueError("fp8 decode weights: need CUDA and a bf16 non-sharded parameter store "
+                         f"(device {device}, {type(store).__name__} {store.compute_dtype})")
+    return Fp8DecodeStore(model, store)
+
+
+def check_fp8_weight_batch(N: int) -> None:
+    if N > _SKINNY_MAX_ROWS:
+        raise ValueError(f"fp8 decode weights: a batch of at most {_SKINNY_MAX_ROWS} sequences, not {N}")
 
 
 def _block_attend(qkv, cache, li, H, hd):
@@ -194,7 +242,7 @@ def prefill_chunked(model, store, input_ids, position_ids, cache, lens, chunk):
     return head_logits(model, rows, store).reshape(N, 1, -1)
 
 
-def kv_decode_forward(model, input_ids, position_ids, cache, lens=None, prefill_chunk=0):
+def kv_decode_forward(model, input_ids, position_ids, cache, lens=None, prefill_chunk=0, weights=None):
     """Incremental forward for decoding: runs only the new tokens (the whole prompt on the first
     call, then one token or a block of tokens per call) through the layers, extends ``cache`` and
     returns the logits of the last new token, ``[N, 1, V]``; the reference recomputes the whole
@@ -210,9 +258,15 @@ def kv_decode_forward(model, input_ids, position_ids, cache, lens=None, prefill_
     own positions (``position_ids`` unused); pad rows past the capacity are not written.
 
     ``prefill_chunk``: with an empty cache and ``0 < prefill_chunk < n``, the prompt runs in
-    blocks of that many tokens (``prefill_chunked``)."""
+    blocks of that many tokens (``prefill_chunked``).
+
+    ``weights``: an ``Fp8DecodeStore`` (``quantize_decode_weights``) for the one-token step; the
+    prompt and blocks of tokens run on the bf16 weights."""
     store = ensure_store(model)
     N, n = input_ids.shape
+    if weights is not None and n == 1 and cache.len > 0:
+        check_fp8_weight_batch(N)
+        store = weights
     dev = input_ids.device
     if cache.ragged and cache.len > 0:
         if lens is not None:
@@ -263,12 +317,15 @@ class GraphDecoder:
     eager decoding is launch-bound (measured in ``bench/generate.py``).  The sampler writes the
     next token straight into the graph's own ``tok`` buffer and into its column of the output
     buffer, and advances the lengths: a replay then needs nothing from the host, ``step()`` with
-    no argument.  Needs a non-sharded parameter store (single GPU / DDP); FSDP decodes eagerly."""
+    no argument.  Needs a non-sharded parameter store (single GPU / DDP); FSDP decodes eagerly.
+    ``weights``: an ``Fp8DecodeStore`` (``quantize_decode_weights``) to run the step's Linears on."""
 
-    def __init__(self, model, cache, sampler=None):
+    def __init__(self, model, cache, sampler=None, weights=None):
         self.model, self.cache, self.sampler = model, cache, sampler
-        self.store = ensure_store(model)
+        self.store = ensure_store(model) if weights is None else weights
         N = cache.k[0].shape[0]
+        if weights is not None:
+            check_fp8_weight_batch(N)
         self.tok = sampler.tok if sampler is not None else torch.zeros(N, 1, device=cache.len_t.device,
                                                                        dtype=torch.int64)
         self.graph = None

@@ -84,6 +84,9 @@ class LMOutput:
 
 
 def _qkv_weight(store, attn):
+    fused = getattr(store, "qkv_weight", None)  # a store that keeps the fused [3E, D] weight itself
+    if fused is not None:
+        return fused(attn)
     wq, wk, wv = (store.weight(m.weight) for m in (attn.to_q, attn.to_k, attn.to_v))
     n = wq.shape[0]
     if (wk.data_ptr() == wq.data_ptr() + wq.numel() * wq.element_size()

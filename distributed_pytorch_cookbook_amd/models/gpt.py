@@ -306,20 +306,22 @@ class TransformerDecoderLM(nn.Module):
                                  f"head_dim {attn.head_dim})")
         return KVCache(self, batch_size, max_len, device, store.compute_dtype, ragged, kv_dtype, k_scale, v_scale)
 
-    def decode(self, input_ids, position_ids, cache, lens=None, prefill_chunk=0):
+    def decode(self, input_ids, position_ids, cache, lens=None, prefill_chunk=0, weights=None):
         """Logits ``[N, 1, V]`` of the last of the new tokens, attending over ``cache`` (extended).
         A ragged cache takes right-padded prompts with their true lengths ``lens`` first (logits of
         row ``lens[n] - 1``), then one token per sequence at its own position, or a right-padded
         block with ``lens`` valid new tokens per sequence (``position_ids`` unused: the positions
         are the cache lengths).  ``prefill_chunk``: a prompt longer than that goes into an empty
-        cache in blocks of that many tokens (0: in one)."""
+        cache in blocks of that many tokens (0: in one).  ``weights``: fp8 weights for the one-token
+        step (``models/decode.py:quantize_decode_weights``)."""
         from .decode import kv_decode_forward
 
-        return kv_decode_forward(self, input_ids, position_ids, cache, lens, prefill_chunk)
+        return kv_decode_forward(self, input_ids, position_ids, cache, lens, prefill_chunk, weights)
 
-    def graph_decoder(self, cache, sampler=None):
+    def graph_decoder(self, cache, sampler=None, weights=None):
         """HIP-graph one-token decode step over ``cache`` (None for a sharded store).  For a ragged
-        cache the graph may end in ``sampler`` (``ops/sample.py:Sampler``)."""
+        cache the graph may end in ``sampler`` (``ops/sample.py:Sampler``).  ``weights``: fp8 weights
+        for the step (``models/decode.py:quantize_decode_weights``)."""
         from ..parallel.store import LocalStore
         from ..ops.attention import decode_supported
         from .decode import GraphDecoder
@@ -334,7 +336,7 @@ class TransformerDecoderLM(nn.Module):
         if (not isinstance(store, LocalStore) or store.compute_dtype != torch.bfloat16
                 or not decode_supported(attn.head_dim)):
             return None
-        return GraphDecoder(self, cache, sampler)
+        return GraphDecoder(self, cache, sampler, weights)
 
 
 PRESETS = {

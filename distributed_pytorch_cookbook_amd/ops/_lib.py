@@ -265,6 +265,21 @@ class SkinnyArgs(ctypes.Structure):
     _fields_ = GemvArgs._fields_ + [("nb", c_int), ("nw", c_int)]
 
 
+class WqArgs(ctypes.Structure):
+    """``wq_gemm.hip:WqArgs``: SkinnyArgs with e4m3 weight bytes ``q`` and their per-row f32 ``scale``."""
+    _fields_ = [
+        ("x", P), ("q", P), ("scale", P), ("bias", P), ("residual", P), ("y", P),
+        ("ldx", LL), ("ldw", LL), ("ldr", LL), ("ldy", LL),
+        ("M", c_int), ("N", c_int), ("Nw", c_int), ("K", c_int),
+        ("act", c_int), ("y_f32", c_int), ("nb", c_int), ("nw", c_int),
+    ]
+
+
+class WqQuantArgs(ctypes.Structure):
+    """``wq_gemm.hip:WqQuantArgs``."""
+    _fields_ = [("w", P), ("inv", P), ("q", P), ("ldw", LL), ("ldq", LL), ("N", c_int), ("K", c_int)]
+
+
 _FUNCS = {
     "dpc_decode_attn": DecodeAttnArgs,
     "dpc_decode_attn_split": DecodeSplitArgs,
@@ -274,6 +289,8 @@ _FUNCS = {
     "dpc_kv_store_fp8": AppendAttnFp8Args,
     "dpc_gemv": GemvArgs,
     "dpc_gemm_skinny": SkinnyArgs,
+    "dpc_gemm_wq8": WqArgs,
+    "dpc_wq_quantize": WqQuantArgs,
     "dpc_sample": SampleArgs,
     "dpc_embedding_bwd_sorted": EmbBwdArgs,
     "dpc_gemm": GemmArgs,

@@ -405,7 +405,13 @@ def _gemm_ref(a, b, a_kmaj, b_kmaj, out, bias, act, act_bwd, aux_in, aux_out, re
 def linear_fwd(x, w, *, bias=None, act=None, residual=None, aux_out=None, out=None,
                out_dtype=torch.bfloat16, aux_deriv=False):
     """y = act(x @ w^T + bias) (+ residual); x [M, K], w [N, K] (nn.Linear layout).
-    ``aux_out`` receives the pre-activation, or act'(pre-activation) with ``aux_deriv``."""
+    ``aux_out`` receives the pre-activation, or act'(pre-activation) with ``aux_deriv``.
+    ``w`` a ``QWeight`` (fp8 weight bytes and per-row scales): ``dpc_gemm_wq8`` for up to 64 rows,
+    ``ValueError`` for anything that kernel does not take."""
+    if isinstance(w, QWeight):
+        if aux_out is not None:
+            raise ValueError("linear_fwd (fp8 weights): no aux_out")
+        return _linear_fwd_wq8(x, w, bias, act_code(act), residual, out, out_dtype)
     if x.is_cuda and aux_out is None and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16:
         M = x.shape[0]
         if M <= _GEMV_ROWS:
@@ -515,6 +521,91 @@ def _linear_fwd_skinny(x, w, bias, act, residual, out, out_dtype, plan=None):
         ldr=residual.stride(0) if residual is not None else 0, ldy=out.stride(0),
         M=M, N=N, Nw=Nw, K=K, act=act, y_f32=int(out.dtype == torch.float32), nb=nb, nw=nw)
     _lib.call("dpc_gemm_skinny", args, x.device)
+    return out
+
+
+# Weight-only FP8 (e4m3) Linears of the decode step (csrc/wq_gemm.hip): the weight stream at one
+# byte per element.  One f32 scale per output row, scale[n] = amax_k |w[n, k]| / 448 (1.0 for a row
+# of zeros), byte = fp8_rne(clamp(float(w) * float32(1 / scale[n]), -448, 448)); the kernel widens
+# the bytes to bf16 in registers (exact), runs the bf16 MFMA and applies scale[n] to the summed
+# accumulator ahead of the bias.  dpc_gemm_wq8 takes every row count 1..64 and every width (the LM
+# head included): there is no other path behind a QWeight.
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+class QWeight:
+    """An fp8 weight: ``q`` [N, K] float8_e4m3fn, ``scale`` [N] f32, w ~ q * scale[:, None]."""
+    __slots__ = ("q", "scale", "shape")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        if q.dim() != 2 or q.dtype != FP8 or scale.dtype != torch.float32 or scale.shape != (q.shape[0],):
+            raise ValueError("QWeight: q [N, K] float8_e4m3fn and scale [N] float32")
+        self.q, self.scale, self.shape = q, scale, q.shape
+
+
+def weight_scales(w: torch.Tensor):
+    """(scale, inv) [N] f32 of ``quantize_weight``: amax / 448 per row (1.0 for a zero row) and its
+    f32 reciprocal."""
+    amax = w.abs().amax(dim=1).float()
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    return scale, 1.0 / scale
+
+
+def weight_quantize_ref(w: torch.Tensor, inv: torch.Tensor) -> torch.Tensor:
+    """The torch twin of ``dpc_wq_quantize``, bit for bit: ``ops/attention.py:kv_quantize_ref``'s
+    expression with one ``inv`` per row."""
+    return (w.float() * inv[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+
+
+def quantize_weight(w: torch.Tensor) -> QWeight:
+    """``w`` [N, K] bf16 on the GPU (K % 16 == 0, rows 16-B aligned) as a ``QWeight``: the scales by
+    torch (set-up, once per weight), the bytes by ``dpc_wq_quantize``."""
+    if not (w.dim() == 2 and w.is_cuda and w.dtype == torch.bfloat16 and w.stride(1) == 1 and w.shape[1] % 16 == 0
+            and w.shape[0] > 0 and w.stride(0) % 8 == 0 and w.stride(0) >= w.shape[1] and w.data_ptr() % 16 == 0):
+        raise ValueError("quantize_weight: a CUDA bf16 [N, K] weight with K % 16 == 0 and 16-B aligned rows")
+    N, K = w.shape
+    scale, inv = weight_scales(w)
+    q = torch.empty(N, K, device=w.device, dtype=FP8)
+    _lib.call("dpc_wq_quantize", _lib.WqQuantArgs(w=w.data_ptr(), inv=inv.data_ptr(), q=q.data_ptr(),
+                                                  ldw=w.stride(0), ldq=K, N=N, K=K), w.device)
+    return QWeight(q, scale)
+
+
+def _wq_ok(x, w, bias, residual, out):
+    q = w.q
+    return (x.dim() == 2 and out.dim() == 2 and x.is_cuda and q.is_cuda and x.dtype == torch.bfloat16
+            and q.shape[1] == x.shape[1] and x.shape[1] % 16 == 0 and out.shape[0] == x.shape[0]
+            and out.dtype in (torch.float32, torch.bfloat16) and x.stride(1) == 1 and q.stride(1) == 1
+            and x.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] and q.stride(0) % 16 == 0
+            and q.stride(0) >= q.shape[1] and x.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0
+            and w.scale.is_cuda and w.scale.is_contiguous()
+            and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() >= q.shape[0]))
+            and (residual is None or (residual.dtype == torch.float32 and residual.stride(1) == 1
+                                      and residual.shape[0] >= x.shape[0] and residual.shape[1] >= q.shape[0]))
+            and out.stride(1) == 1 and 0 < q.shape[0] <= out.shape[1])
+
+
+def _linear_fwd_wq8(x, w, bias, act, residual, out, out_dtype, plan=None):
+    """``dpc_gemm_wq8`` (csrc/wq_gemm.hip) on a ``QWeight``; operands the kernel does not take raise.
+    The plan is ``skinny_plan``'s, or ``plan``: one of SKINNY_PLANS (tests, measurements)."""
+    M, K = x.shape
+    Nw = w.shape[0]
+    if M > _SKINNY_MAX_ROWS:
+        raise ValueError(f"linear_fwd (fp8 weights): at most {_SKINNY_MAX_ROWS} rows, not {M}")
+    if out is None:
+        out = torch.empty(M, Nw, device=x.device, dtype=out_dtype)
+    if not (M > 0 and _wq_ok(x, w, bias, residual, out)):
+        raise ValueError("linear_fwd (fp8 weights): operands the kernel does not take (CUDA bf16 x, K % 16 == 0, "
+                         "16-B aligned rows, f32 bias / residual)")
+    N = out.shape[1]
+    nb, nw = plan or skinny_plan(M, N, K, torch.cuda.get_device_properties(x.device).multi_processor_count)
+    args = _lib.WqArgs(
+        x=x.data_ptr(), q=w.q.data_ptr(), scale=w.scale.data_ptr(), bias=_lib.ptr(bias), residual=_lib.ptr(residual),
+        y=out.data_ptr(), ldx=x.stride(0), ldw=w.q.stride(0),
+        ldr=residual.stride(0) if residual is not None else 0, ldy=out.stride(0),
+        M=M, N=N, Nw=Nw, K=K, act=act, y_f32=int(out.dtype == torch.float32), nb=nb, nw=nw)
+    _lib.call("dpc_gemm_wq8", args, x.device)
     return out
 
 

@@ -49,19 +49,22 @@ def prepare_batch(batch, pad_id: int, device):
 @torch.inference_mode()
 def generate(model, prompt: str, tokenizer, device, max_new_tokens: int = 20, use_cache: bool = True,
              temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-             prefill_chunk: int = 0, kv_dtype=None) -> str:
+             prefill_chunk: int = 0, kv_dtype=None, weight_dtype=None) -> str:
     """``prefill_chunk``: the KV-cache decode takes a prompt longer than that in blocks of that many
     tokens (0: in one).  ``kv_dtype``: "fp8" for the 1-byte KV cache (``new_kv_cache``); a model
-    without ``decode`` ignores it, as it ignores the cache."""
+    without ``decode`` ignores it, as it ignores the cache.  ``weight_dtype``: "fp8" runs the
+    one-token steps on an e4m3 copy of the Linear weights, made for this call
+    (``models/decode.py:quantize_decode_weights``: CUDA, a bf16 non-sharded store)."""
     if temperature > 0 or top_k > 0 or top_p < 1.0:  # sampling: the batched loop with one prompt
         return generate_batch(model, [prompt], tokenizer, device, max_new_tokens, temperature, top_k, top_p, seed,
-                              prefill_chunk, kv_dtype)[0]
+                              prefill_chunk, kv_dtype, weight_dtype)[0]
     batch = tokenizer([prompt], truncation=True, max_length=256, return_tensors="pt")
     input_ids = batch["input_ids"].to(device)
     # the learned position table bounds the context: slide a window past it
     max_pos = getattr(model, "max_position_embeddings", None) or 1 << 30
     if use_cache and hasattr(model, "decode") and input_ids.shape[1] + max_new_tokens <= max_pos:
-        return _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk, kv_dtype)
+        return _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk, kv_dtype,
+                                weight_dtype)
     new = _recompute(model, input_ids, device, max_new_tokens, max_pos, tokenizer.eos_token_id,
                      lambda logits, i: int(logits.argmax(dim=-1)))
     return tokenizer.decode(input_ids[0].tolist() + new, skip_special_tokens=True)
@@ -73,16 +76,31 @@ def _kv_kw(kv_dtype):
     return {} if kv_dtype in (None, "bf16") else {"kv_dtype": kv_dtype}
 
 
-def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk=0, kv_dtype=None):
+def _decode_weights(model, weight_dtype, N):
+    """The one-token steps' weights: None for the store's own, or an fp8 copy of them as they are
+    now -- made per call, never kept: the recipes sample between epochs of training."""
+    if weight_dtype in (None, "bf16"):
+        return None
+    if weight_dtype != "fp8":
+        raise ValueError(f"weight_dtype must be None, 'bf16' or 'fp8', not {weight_dtype!r}")
+    from ..models.decode import check_fp8_weight_batch, quantize_decode_weights
+
+    check_fp8_weight_batch(N)
+    return quantize_decode_weights(model)
+
+
+def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk=0, kv_dtype=None,
+                     weight_dtype=None):
     """KV-cache greedy decode: one prefill of the prompt, then one token per forward (same
     tokens as the full-recompute loop while the context fits the position table)."""
+    wkw = {} if weight_dtype in (None, "bf16") else {"weights": _decode_weights(model, weight_dtype, 1)}
     cache = model.new_kv_cache(1, input_ids.shape[1] + max_new_tokens, **_kv_kw(kv_dtype))
     s = input_ids.shape[1]
     logits = model.decode(input_ids, torch.arange(s, device=device).unsqueeze(0), cache, prefill_chunk=prefill_chunk)
     out = input_ids[0].tolist()
     step = None
     if device.type == "cuda" and hasattr(model, "graph_decoder"):
-        step = model.graph_decoder(cache)  # None if the store is sharded (FSDP)
+        step = model.graph_decoder(cache, **wkw)  # None if the store is sharded (FSDP)
     for i in range(max_new_tokens):
         new_token = int(logits[0, -1].argmax(dim=-1))
         if new_token == tokenizer.eos_token_id:
@@ -94,7 +112,8 @@ def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefil
         if step is not None:
             logits = step.step(tok)
         else:
-            logits = model.decode(tok, torch.full((1, 1), len(out) - 1, device=device, dtype=torch.long), cache)
+            logits = model.decode(tok, torch.full((1, 1), len(out) - 1, device=device, dtype=torch.long), cache,
+                                  **wkw)
     return tokenizer.decode(out, skip_special_tokens=True)
 
 
@@ -132,12 +151,14 @@ DONE_POLL = 8  # steps between two reads of the done flags
 
 @torch.inference_mode()
 def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, temperature: float = 0.0,
-                   top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None) -> list:
+                   top_k: int = 0, top_p: float = 1.0, seed: int = 0, prefill_chunk: int = 0, kv_dtype=None,
+                   weight_dtype=None) -> list:
     """Continuations of ``prompts`` (a list of strings), sampled with ``temperature`` / ``top_k`` /
     ``top_p`` from the counter-based stream of ``seed`` (row n of the batch draws
     ``sample_uniform(seed, n, step)``: the same arguments give the same text, on every rank).
     ``prefill_chunk``: the padded prompts go into the cache in blocks of that many tokens (0: in one).
-    ``kv_dtype``: "fp8" for the 1-byte KV cache (ignored without ``decode``)."""
+    ``kv_dtype``: "fp8" for the 1-byte KV cache (ignored without ``decode``).  ``weight_dtype``: "fp8"
+    for the one-token steps on e4m3 weights, as in ``generate`` (at most 64 prompts)."""
     from ..ops.sample import Sampler
 
     device = torch.device(device)
@@ -151,7 +172,7 @@ def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, 
     max_pos = getattr(model, "max_position_embeddings", None) or 1 << 30
     sampler = Sampler(N, max_new_tokens, device, temperature, top_k, top_p, seed, eos)
     if hasattr(model, "decode") and max(lens) + max_new_tokens <= max_pos:
-        _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk, kv_dtype)
+        _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk, kv_dtype, weight_dtype)
         new = sampler.sequences()
     else:
         new = [_recompute(model, t.view(1, -1).to(device), device, max_new_tokens, max_pos, eos,
@@ -159,10 +180,12 @@ def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, 
     return [tokenizer.decode(t.tolist() + g, skip_special_tokens=True) for t, g in zip(ids, new)]
 
 
-def _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk=0, kv_dtype=None):
+def _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_chunk=0, kv_dtype=None,
+                   weight_dtype=None):
     """One prefill of the right-padded prompts into a ragged KV cache, then one token per sequence
     per step: a replayed HIP graph ending in the sampler where the model has one, else eagerly."""
     N, S = len(ids), max(lens)
+    wkw = {} if weight_dtype in (None, "bf16") else {"weights": _decode_weights(model, weight_dtype, N)}
     padded = torch.zeros(N, S, dtype=torch.int64)
     for n, t in enumerate(ids):
         padded[n, :lens[n]] = t
@@ -171,14 +194,14 @@ def _sample_cached(model, ids, lens, sampler, device, max_new_tokens, prefill_ch
     sampler(logits[:, 0])  # (the prefill has set the lengths: token 0 goes to position lens[n])
     dec = None
     if device.type == "cuda" and hasattr(model, "graph_decoder"):
-        dec = model.graph_decoder(cache, sampler)  # None if the store is sharded (FSDP) or f32
+        dec = model.graph_decoder(cache, sampler, **wkw)  # None if the store is sharded (FSDP) or f32
     for i in range(1, max_new_tokens):
         if i % DONE_POLL == 0 and bool(sampler.done.all()):
             break
         if dec is not None:
             dec.step()
         else:
-            sampler(model.decode(sampler.tok, None, cache)[:, 0])
+            sampler(model.decode(sampler.tok, None, cache, **wkw)[:, 0])
 
 
 def _sampled_pick(sampler, row):
