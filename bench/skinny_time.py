@@ -16,8 +16,13 @@ weight bytes the product must read and those bytes over the time.  One JSON line
 (``dpc_gemm_wq8``, csrc/wq_gemm.hip) on a quantised copy of every weight copy, under both plans;
 its weight bytes are half.
 
+``--norm``: the products that consume a LayerNorm (QKV, up-projection, LM head) on the f32 residual
+stream: ``layernorm_fwd`` then ``linear_fwd`` (two launches) against ``linear_fwd(norm=)``
+(``dpc_ln_linear``, csrc/ln_linear.hip, one launch), at the row counts that kernel takes, on bf16
+weights or with ``--weight_dtype fp8`` on the quantised ones.
+
     python bench/skinny_time.py [--rows 1 8 16 17 32 48 64] [--models gpt2-small gpt2-xl] [--plans]
-                                [--weight_dtype fp8]
+                                [--weight_dtype fp8] [--norm]
 """
 import argparse
 import json
@@ -29,6 +34,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from distributed_pytorch_cookbook_amd.ops import gemm as G  # noqa: E402
+from distributed_pytorch_cookbook_amd.ops.norm import layernorm_fwd  # noqa: E402
 
 DIMS = {"gpt2-small": 768, "gpt2-xl": 1600}
 VOCAB, VOCAB_LD = 50257, 50304
@@ -47,6 +53,9 @@ def main():
     ap.add_argument("--models", nargs="+", default=list(DIMS))
     ap.add_argument("--plans", action="store_true", help="also every instantiated (columns, waves) plan")
     ap.add_argument("--weight_dtype", default="bf16", choices=["bf16", "fp8"], help="fp8: also dpc_gemm_wq8")
+    ap.add_argument("--norm", action="store_true",
+                    help="instead: LayerNorm + Linear (two launches) against dpc_ln_linear (one), on the products "
+                         "that consume a LayerNorm, with the weights of --weight_dtype")
     ap.add_argument("--cache_mb", type=int, default=768, help="weight copies cover at least this much")
     ap.add_argument("--min_calls", type=int, default=24)
     ap.add_argument("--rounds", type=int, default=5)
@@ -68,6 +77,8 @@ def main():
     for model in a.models:
         D = DIMS[model]
         for name, Nw, N, K, has_bias, act, has_res in shapes(D):
+            if a.norm and has_res:  # (no LayerNorm feeds the out- and down-projections)
+                continue
             w_bytes = Nw * K * 2
             copies = max(a.min_calls, -(-a.cache_mb * 2**20 // w_bytes))
             ws = [(torch.randn(Nw, K, device=dev) / K ** 0.5).bfloat16() for _ in range(copies)]
@@ -86,7 +97,18 @@ def main():
                     variants.append((f"skinny {pl[0]}x{pl[1]}" + (" (plan)" if pl == plan else ""),
                                      lambda w, pl=pl: G._linear_fwd_skinny(x, w, bias, act, res, out, odt, plan=pl)))
                 variants = [(vname, fn, ws, w_bytes) for vname, fn in variants]
-                if qs is not None:
+                if a.norm:
+                    # the LayerNorm's consumers only, on the f32 residual stream: one fused launch
+                    # against LayerNorm then what linear_fwd runs at that row count
+                    if not G.ln_linear_ok(M, K, (qs or ws)[0]):
+                        continue
+                    xf, gamma, beta = torch.randn(M, K, device=dev), torch.rand(K, device=dev) + 0.5, torch.randn(K, device=dev)
+                    norm = (gamma, beta, 1e-5)
+                    variants = [("ln + linear", lambda w: G.linear_fwd(layernorm_fwd(xf, *norm)[0], w, bias=bias, act=act, out=out),
+                                 qs or ws, w_bytes // (2 if qs else 1)),
+                                ("ln_linear", lambda w: G.linear_fwd(xf, w, bias=bias, act=act, out=out, norm=norm),
+                                 qs or ws, w_bytes // (2 if qs else 1))]
+                elif qs is not None:
                     for pl in G.SKINNY_PLANS:
                         variants.append((f"fp8 {pl[0]}x{pl[1]}" + (" (plan)" if pl == plan else ""),
                                          lambda w, pl=pl: G._linear_fwd_wq8(x, w, bias, act, res, out, odt, plan=pl),

@@ -14,7 +14,8 @@ import torch
 
 from ..ops.attention import FP8, append_attention, attention_fwd, decode_attention, kv_cache_store_fp8
 from ..ops.gemm import _SKINNY_MAX_ROWS, act_code, quantize_weight
-from .fused import _layer_forward, _qkv_weight, ensure_store, head_logits, last_rows, run_embeddings
+from .fused import (_layer_forward, _layer_forward_ln_linear, _qkv_weight, ensure_store, head_logits, last_rows,
+                    ln_linear_step, run_embeddings)
 
 
 class KVCache:
@@ -180,14 +181,18 @@ def _step_attend(qkv, cache, li, H, hd):
 def _run_layers(model, store, x, N, n, cache, attend):
     """Every layer on the n new tokens of each sequence, ``attend(qkv, cache, li, H, hd) -> (o, lse)``
     in place of the self-attention; the unit boundaries are reported to the store (a sharded
-    store gathers its weights there)."""
+    store gathers its weights there).  One token per sequence (n = 1) runs each LayerNorm inside
+    the Linear that consumes it where ``ln_linear_step`` holds for the layer's weights."""
     act = act_code(model.activation)
     for li, layer in enumerate(model.decoder.layers):
         H, hd = layer.attn.heads, layer.attn.head_dim
         u = layer._unit_id
         store.pre_forward(u)
-        x, _ = _layer_forward(x, None, layer, store, N, n, act, False, (None, None),
-                              attend=lambda qkv: attend(qkv, cache, li, H, hd))
+        if n == 1 and ln_linear_step(store, x, _qkv_weight(store, layer.attn), store.weight(layer.fc.up_proj.weight)):
+            x = _layer_forward_ln_linear(x, layer, store, act, lambda qkv: attend(qkv, cache, li, H, hd))
+        else:
+            x, _ = _layer_forward(x, None, layer, store, N, n, act, False, (None, None),
+                                  attend=lambda qkv: attend(qkv, cache, li, H, hd))
         store.post_forward(u, False)
     return x
 
@@ -201,7 +206,7 @@ def decode_step(model, store, cache, tok, sampler=None):
     N = tok.shape[0]
     x = run_embeddings(model, store, tok, cache.positions(N), False)
     x = _run_layers(model, store, x, N, 1, cache, _step_attend)
-    logits = head_logits(model, x, store)
+    logits = head_logits(model, x, store, one_token=True)
     if sampler is not None:
         sampler(logits, lens=cache.len_t)
     else:
@@ -307,7 +312,7 @@ def kv_decode_forward(model, input_ids, position_ids, cache, lens=None, prefill_
         rows = _last_valid_rows(x, N, n, lens, dev)
     else:
         rows = last_rows(x, N, n)
-    return head_logits(model, rows, store).reshape(N, 1, -1)
+    return head_logits(model, rows, store, one_token=n == 1).reshape(N, 1, -1)
 
 
 class GraphDecoder:

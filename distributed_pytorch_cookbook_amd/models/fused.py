@@ -31,8 +31,9 @@ from ..ops.attention import attention_bwd, attention_fwd
 from ..ops.elementwise import bias_act_bwd
 from ..ops.dropout import dropout_residual
 from ..ops.embedding import embedding_bwd, embedding_fwd
+from ..ops import gemm as _gemm
 from ..ops.gemm import (ACT_GELU, ACT_MUL, ACT_NONE, ACT_RELU, act_code, linear_dgrad, linear_fwd, linear_wgrad,
-                        register_side_stream)
+                        ln_linear_ok, register_side_stream)
 from ..ops.loss import cross_entropy_fused, cross_entropy_rows
 from ..ops.norm import layernorm_bwd, layernorm_fwd
 
@@ -181,6 +182,39 @@ class _EmbedFn(torch.autograd.Function):
 
 # DPC_FUSE_OUT_LN=0: out-projection with the bias + residual GEMM epilogue and a separate LN2
 _FUSE_OUT_LN = os.environ.get("DPC_FUSE_OUT_LN", "1") == "1"
+
+
+# The one-token decode step: each LayerNorm inside the launch of the Linear that consumes it
+# (ops/csrc/ln_linear.hip) -- a layer is 5 launches instead of 7, the head 1 instead of 2 -- up to
+# ops/gemm.py:LN_LINEAR_ROWS rows (0 as shipped: see there).  DPC_LN_LINEAR=0: the separate
+# LayerNorm launches whatever the row count says (A/B only)
+_LN_LINEAR = os.environ.get("DPC_LN_LINEAR", "1") == "1"
+
+
+def ln_linear_step(store, x, *weights) -> bool:
+    """Whether a one-token step over the f32 rows x runs its LayerNorms inside ``weights``' Linears:
+    a bf16 store on the GPU, at most LN_LINEAR_ROWS rows, no product wider than LN_LINEAR_MAX_N,
+    shapes the kernel takes."""
+    M, K = x.shape
+    return (_LN_LINEAR and x.is_cuda and x.dtype == torch.float32 and store.compute_dtype == torch.bfloat16
+            and M <= _gemm.LN_LINEAR_ROWS
+            and all(w.shape[0] <= _gemm.LN_LINEAR_MAX_N and ln_linear_ok(M, K, w) for w in weights))
+
+
+def _layer_forward_ln_linear(x, layer, store, act, attend):
+    """``_layer_forward`` of an inference step of a few rows (``ln_linear_step``) in 5 launches:
+    LN1 + QKV, attend, out-projection (bias + residual epilogue, f32), LN2 + up-projection, down."""
+    attn, fc = layer.attn, layer.fc
+    w = store.weight
+    cdt = store.compute_dtype
+    qkv = linear_fwd(x, _qkv_weight(store, attn), out_dtype=cdt,
+                     norm=(w(layer.norm1.weight), w(layer.norm1.bias), LN_EPS))
+    o, _ = attend(qkv)
+    x2 = linear_fwd(o, w(attn.to_out.weight), bias=w(attn.to_out.bias), residual=x, out_dtype=torch.float32)
+    uact = linear_fwd(x2, w(fc.up_proj.weight), bias=w(fc.up_proj.bias), act=act, out_dtype=cdt,
+                      norm=(w(layer.norm2.weight), w(layer.norm2.bias), LN_EPS))
+    return linear_fwd(uact, w(fc.down_proj.weight), bias=w(fc.down_proj.bias), act=act, residual=x2,
+                      out_dtype=torch.float32)
 
 
 def _layer_forward(x, mask, layer, store, N, S, act, training, drops, attend=None, pre=None, fuse_out=None):
@@ -543,9 +577,11 @@ class _HeadFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None, None
 
 
-def head_logits(model, x, store, tail=None):
+def head_logits(model, x, store, tail=None, one_token=False):
     """Inference head: logits [T, V] (view of a row-padded buffer), no loss.  ``tail``: the last
-    layer's, whose FFN output the final norm adds to the residual stream (x then unwritten)."""
+    layer's, whose FFN output the final norm adds to the residual stream (x then unwritten).
+    ``one_token``: the head of a one-token step, which takes the final norm into the LM head's
+    launch where ``ln_linear_step`` holds."""
     w = store.weight
     unit = model._head_unit_id
     store.pre_forward(unit)
@@ -553,9 +589,14 @@ def head_logits(model, x, store, tail=None):
     pending = None
     if tail is not None and tail.pending is not None:
         pending, tail.pending = tail.pending, None
-    hf, _, _ = _ln_in(x, pending, w(model.norm_out.weight), w(model.norm_out.bias), store.compute_dtype)
     ld = vocab_ld(V) if x.is_cuda else V
     buf = torch.empty(x.shape[0], ld, device=x.device, dtype=store.compute_dtype)
+    if one_token and pending is None and ln_linear_step(store, x, w(model.lm_head.weight)):
+        linear_fwd(x, w(model.lm_head.weight), out=buf,
+                   norm=(w(model.norm_out.weight), w(model.norm_out.bias), LN_EPS))
+        store.post_forward(unit, False)
+        return buf[:, :V]
+    hf, _, _ = _ln_in(x, pending, w(model.norm_out.weight), w(model.norm_out.bias), store.compute_dtype)
     linear_fwd(hf, w(model.lm_head.weight), out=buf)
     store.post_forward(unit, False)
     return buf[:, :V]

@@ -275,6 +275,17 @@ class WqArgs(ctypes.Structure):
     ]
 
 
+class LnLinearArgs(ctypes.Structure):
+    """``ln_linear.hip:LnLinearArgs``: f32 ``x`` normalised by ``gamma`` / ``beta`` / ``eps`` on its way
+    into a SkinnyArgs (``scale`` null) or WqArgs (``scale`` set) product."""
+    _fields_ = [
+        ("x", P), ("gamma", P), ("beta", P), ("w", P), ("scale", P), ("bias", P), ("residual", P), ("y", P),
+        ("ldx", LL), ("ldw", LL), ("ldr", LL), ("ldy", LL),
+        ("M", c_int), ("N", c_int), ("Nw", c_int), ("K", c_int), ("eps", c_float),
+        ("act", c_int), ("y_f32", c_int), ("nb", c_int), ("nw", c_int),
+    ]
+
+
 class WqQuantArgs(ctypes.Structure):
     """``wq_gemm.hip:WqQuantArgs``."""
     _fields_ = [("w", P), ("inv", P), ("q", P), ("ldw", LL), ("ldq", LL), ("N", c_int), ("K", c_int)]
@@ -291,6 +302,7 @@ _FUNCS = {
     "dpc_gemm_skinny": SkinnyArgs,
     "dpc_gemm_wq8": WqArgs,
     "dpc_wq_quantize": WqQuantArgs,
+    "dpc_ln_linear": LnLinearArgs,
     "dpc_sample": SampleArgs,
     "dpc_embedding_bwd_sorted": EmbBwdArgs,
     "dpc_gemm": GemmArgs,

@@ -403,11 +403,18 @@ def _gemm_ref(a, b, a_kmaj, b_kmaj, out, bias, act, act_bwd, aux_in, aux_out, re
 
 # ---------------------------------------------------------------- Linear-shaped helpers
 def linear_fwd(x, w, *, bias=None, act=None, residual=None, aux_out=None, out=None,
-               out_dtype=torch.bfloat16, aux_deriv=False):
+               out_dtype=torch.bfloat16, aux_deriv=False, norm=None):
     """y = act(x @ w^T + bias) (+ residual); x [M, K], w [N, K] (nn.Linear layout).
     ``aux_out`` receives the pre-activation, or act'(pre-activation) with ``aux_deriv``.
     ``w`` a ``QWeight`` (fp8 weight bytes and per-row scales): ``dpc_gemm_wq8`` for up to 64 rows,
-    ``ValueError`` for anything that kernel does not take."""
+    ``ValueError`` for anything that kernel does not take.
+    ``norm=(gamma, beta, eps)``: x is the f32 residual stream and the product takes
+    bf16(LayerNorm(x)) in the same launch (``dpc_ln_linear``, w bf16 or a ``QWeight``); operands
+    that kernel does not take (``ln_linear_ok``) are a ``ValueError``, never two launches."""
+    if norm is not None:
+        if aux_out is not None:
+            raise ValueError("linear_fwd (norm=): no aux_out")
+        return _linear_fwd_ln(x, w, norm, bias, act_code(act), residual, out, out_dtype)
     if isinstance(w, QWeight):
         if aux_out is not None:
             raise ValueError("linear_fwd (fp8 weights): no aux_out")
@@ -606,6 +613,83 @@ def _linear_fwd_wq8(x, w, bias, act, residual, out, out_dtype, plan=None):
         ldr=residual.stride(0) if residual is not None else 0, ldy=out.stride(0),
         M=M, N=N, Nw=Nw, K=K, act=act, y_f32=int(out.dtype == torch.float32), nb=nb, nw=nw)
     _lib.call("dpc_gemm_wq8", args, x.device)
+    return out
+
+
+# LayerNorm fused into the Linear that consumes it (csrc/ln_linear.hip): every workgroup of the
+# few-row split normalises the f32 rows into LDS as bf16 and reads its MFMA B operand from there,
+# so LN + Linear is one launch.  The kernel takes up to _LN_LINEAR_MAX_ROWS rows while the image
+# [M][K + pad] and the partials fit a workgroup's LDS.
+_LN_LINEAR_MAX_ROWS = 32
+_LN_LINEAR_LDS = 160 * 1024
+# The row count up to which the one-token step uses it (models/fused.py:ln_linear_step), and the
+# widest product it takes there.  0: the step keeps its separate LayerNorm launches.  Measured on
+# the MI355X (docs/GENERATION.md): the graphed GPT-2 small step is 5.9 % (bf16 weights) and 2.9 %
+# (e4m3) faster at batch 1 with the fused layers, the GPT-2 XL step 1.0 % and 0.8 % SLOWER, at a
+# run-to-run spread of 0.1 %; the step changes only if it gains on both.  The LM head over the
+# vocabulary loses as a single product at one row with either weight type: no width above
+# LN_LINEAR_MAX_N is fused at any setting of the row count.
+LN_LINEAR_ROWS = 0
+LN_LINEAR_MAX_N = 32768
+
+
+def _ln_image_ld(K: int) -> int:
+    """Row stride of the LDS image in elements (ln_linear.hip:lnl_ld): an odd number of 16-B units."""
+    return K + (8 if (K // 8) % 2 == 0 else 16)
+
+
+def ln_linear_ok(M: int, K: int, w) -> bool:
+    """Whether ``linear_fwd(x [M, K] f32, w, norm=...)`` takes these shapes (shapes and weight type
+    only: alignment and the epilogue operands are checked at the call)."""
+    fp8 = isinstance(w, QWeight)
+    if not fp8 and not (torch.is_tensor(w) and w.dim() == 2 and w.dtype == torch.bfloat16):
+        return False
+    return (0 < M <= _LN_LINEAR_MAX_ROWS and K > 0 and K % (16 if fp8 else 8) == 0 and w.shape[1] == K
+            and w.shape[0] > 0 and M * _ln_image_ld(K) * 2 + 8192 * -(-M // 16) <= _LN_LINEAR_LDS)
+
+
+def _linear_fwd_ln(x, w, norm, bias, act, residual, out, out_dtype, plan=None):
+    """``dpc_ln_linear`` (csrc/ln_linear.hip); operands the kernel does not take raise.  The plan is
+    ``skinny_plan``'s, or ``plan``: one of SKINNY_PLANS (tests, measurements)."""
+    gamma, beta, eps = norm
+    fp8 = isinstance(w, QWeight)
+    wt = w.q if fp8 else w
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32):
+        raise ValueError("linear_fwd (norm=): x must be a CUDA f32 [M, K] tensor (the residual stream)")
+    if not (fp8 or (torch.is_tensor(w) and w.dtype == torch.bfloat16)):
+        raise ValueError("linear_fwd (norm=): w must be bf16 or a QWeight")
+    M, K = x.shape
+    if not 0 < M <= _LN_LINEAR_MAX_ROWS:
+        raise ValueError(f"linear_fwd (norm=): 1 to {_LN_LINEAR_MAX_ROWS} rows, not {M}")
+    if K % (16 if fp8 else 8) or wt.dim() != 2 or wt.shape[1] != K:
+        raise ValueError(f"linear_fwd (norm=): K % {16 if fp8 else 8} == 0 and w [N, K], not K = {K}, w {tuple(wt.shape)}")
+    if not ln_linear_ok(M, K, w):
+        raise ValueError(f"linear_fwd (norm=): {M} rows of K = {K} do not fit the LDS image")
+    Nw = wt.shape[0]
+    if out is None:
+        out = torch.empty(M, Nw, device=x.device, dtype=out_dtype)
+    lw = 16 if fp8 else 8
+    if not (x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= K and x.data_ptr() % 16 == 0
+            and wt.is_cuda and wt.stride(1) == 1 and wt.stride(0) % lw == 0 and wt.stride(0) >= K
+            and wt.data_ptr() % 16 == 0 and (not fp8 or (w.scale.is_cuda and w.scale.is_contiguous()))
+            and all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == K
+                    and t.data_ptr() % 16 == 0 for t in (gamma, beta))
+            and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() >= Nw))
+            and (residual is None or (residual.dtype == torch.float32 and residual.stride(1) == 1
+                                      and residual.shape[0] >= M and residual.shape[1] >= Nw))
+            and out.dim() == 2 and out.shape[0] == M and out.stride(1) == 1 and Nw <= out.shape[1]
+            and out.dtype in (torch.float32, torch.bfloat16)):
+        raise ValueError("linear_fwd (norm=): operands the kernel does not take (16-B aligned rows, f32 gamma / beta "
+                         "[K] / bias / residual, bf16 or f32 out)")
+    N = out.shape[1]
+    nb, nw = plan or skinny_plan(M, N, K, torch.cuda.get_device_properties(x.device).multi_processor_count)
+    args = _lib.LnLinearArgs(
+        x=x.data_ptr(), gamma=gamma.data_ptr(), beta=beta.data_ptr(), w=wt.data_ptr(),
+        scale=w.scale.data_ptr() if fp8 else None, bias=_lib.ptr(bias), residual=_lib.ptr(residual),
+        y=out.data_ptr(), ldx=x.stride(0), ldw=wt.stride(0),
+        ldr=residual.stride(0) if residual is not None else 0, ldy=out.stride(0),
+        M=M, N=N, Nw=Nw, K=K, eps=float(eps), act=act, y_f32=int(out.dtype == torch.float32), nb=nb, nw=nw)
+    _lib.call("dpc_ln_linear", args, x.device)
     return out
 
 
