@@ -7,13 +7,13 @@ ms per step, and ms per token per sequence = that / B).
 
     python bench/generate.py [--model gpt2-small] [--ctx 1000] [--tokens 20]
                              [--batch 8 --temperature 0.8 --top_k 50 --top_p 0.9]
-                             [--prefill_chunk 512] [--kv_dtype fp8] [--weight_dtype fp8]
+                             [--prefill_chunk 512] [--kv_dtype fp8] [--weight_dtype fp8|fp4]
 
 ``prefill_ms``: the prompt into an empty cache (the median of three, after a warm-up prefill), in
 blocks of ``--prefill_chunk`` tokens where given (every prefill of the KV-cache sections then runs
 in blocks, the eager ``kv_cache`` one included); the position table grows with ``--ctx``.
-``--weight_dtype fp8``: the one-token steps of the KV-cache sections run on an e4m3 copy of the
-Linear weights (``quantize_decode_weights``; ``quantize_ms``: the one-time cost of making it).
+``--weight_dtype fp8`` / ``fp4``: the one-token steps of the KV-cache sections run on an e4m3 / MXFP4
+copy of the Linear weights (``quantize_decode_weights``; ``quantize_ms``: the one-time cost of making it).
 """
 import argparse
 import json
@@ -39,7 +39,7 @@ def main():
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--prefill_chunk", type=int, default=0, help="prefill in blocks of this many tokens (0: in one)")
     ap.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"], help="element of the KV cache")
-    ap.add_argument("--weight_dtype", default="bf16", choices=["bf16", "fp8"], help="weights of the one-token steps")
+    ap.add_argument("--weight_dtype", default="bf16", choices=["bf16", "fp8", "fp4"], help="weights of the one-token steps")
     a = ap.parse_args()
     kv = {"kv_dtype": a.kv_dtype}
     p = PRESETS[a.model]
@@ -51,13 +51,13 @@ def main():
     m.eval()
     res = {}
     wkw = {}
-    if a.weight_dtype == "fp8":
+    if a.weight_dtype != "bf16":
         from distributed_pytorch_cookbook_amd.models.decode import quantize_decode_weights
 
-        quantize_decode_weights(m)  # (warm-up: library load, allocator)
+        quantize_decode_weights(m, a.weight_dtype)  # (warm-up: library load, allocator)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        wkw = {"weights": quantize_decode_weights(m)}
+        wkw = {"weights": quantize_decode_weights(m, a.weight_dtype)}
         torch.cuda.synchronize()
         res["quantize_ms"] = (time.perf_counter() - t0) * 1e3
     for last_only in (() if a.graph_only else (False, True)):

@@ -14,7 +14,9 @@ weight bytes the product must read and those bytes over the time.  One JSON line
 
 ``--weight_dtype fp8``: beside what bf16 weights run at that row count, the fp8-weight kernel
 (``dpc_gemm_wq8``, csrc/wq_gemm.hip) on a quantised copy of every weight copy, under both plans;
-its weight bytes are half.
+its weight bytes are half.  ``--weight_dtype fp4``: the fp8-weight kernel and the MXFP4-weight kernel
+(``dpc_gemm_wq4``, csrc/wq4_gemm.hip, a quarter of the bytes) side by side; the copies are then
+counted so that the fp4 ones alone exceed the caches.
 
 ``--norm``: the products that consume a LayerNorm (QKV, up-projection, LM head) on the f32 residual
 stream: ``layernorm_fwd`` then ``linear_fwd`` (two launches) against ``linear_fwd(norm=)``
@@ -22,7 +24,7 @@ stream: ``layernorm_fwd`` then ``linear_fwd`` (two launches) against ``linear_fw
 weights or with ``--weight_dtype fp8`` on the quantised ones.
 
     python bench/skinny_time.py [--rows 1 8 16 17 32 48 64] [--models gpt2-small gpt2-xl] [--plans]
-                                [--weight_dtype fp8] [--norm]
+                                [--weight_dtype fp8|fp4] [--norm]
 """
 import argparse
 import json
@@ -52,7 +54,8 @@ def main():
     ap.add_argument("--rows", type=int, nargs="+", default=[1, 8, 16, 17, 32, 48, 64])
     ap.add_argument("--models", nargs="+", default=list(DIMS))
     ap.add_argument("--plans", action="store_true", help="also every instantiated (columns, waves) plan")
-    ap.add_argument("--weight_dtype", default="bf16", choices=["bf16", "fp8"], help="fp8: also dpc_gemm_wq8")
+    ap.add_argument("--weight_dtype", default="bf16", choices=["bf16", "fp8", "fp4"],
+                    help="fp8: also dpc_gemm_wq8; fp4: also dpc_gemm_wq8 and dpc_gemm_wq4")
     ap.add_argument("--norm", action="store_true",
                     help="instead: LayerNorm + Linear (two launches) against dpc_ln_linear (one), on the products "
                          "that consume a LayerNorm, with the weights of --weight_dtype")
@@ -80,9 +83,10 @@ def main():
             if a.norm and has_res:  # (no LayerNorm feeds the out- and down-projections)
                 continue
             w_bytes = Nw * K * 2
-            copies = max(a.min_calls, -(-a.cache_mb * 2**20 // w_bytes))
+            copies = max(a.min_calls, -(-a.cache_mb * 2**20 // (w_bytes // 4 if a.weight_dtype == "fp4" else w_bytes)))
             ws = [(torch.randn(Nw, K, device=dev) / K ** 0.5).bfloat16() for _ in range(copies)]
-            qs = [G.quantize_weight(w) for w in ws] if a.weight_dtype == "fp8" else None
+            qs = [G.quantize_weight(w) for w in ws] if a.weight_dtype != "bf16" else None
+            q4s = [G.quantize_weight(w, "fp4") for w in ws] if a.weight_dtype == "fp4" else None
             bias = torch.randn(Nw, device=dev) if has_bias else None
             for M in a.rows:
                 x = torch.randn(M, K, device=dev).bfloat16()
@@ -113,6 +117,10 @@ def main():
                         variants.append((f"fp8 {pl[0]}x{pl[1]}" + (" (plan)" if pl == plan else ""),
                                          lambda w, pl=pl: G._linear_fwd_wq8(x, w, bias, act, res, out, odt, plan=pl),
                                          qs, w_bytes // 2))
+                    for pl in (G.SKINNY_PLANS if q4s is not None else ()):
+                        variants.append((f"fp4 {pl[0]}x{pl[1]}" + (" (plan)" if pl == plan else ""),
+                                         lambda w, pl=pl: G._linear_fwd_wq4(x, w, bias, act, res, out, odt, plan=pl),
+                                         q4s, w_bytes // 4 + w_bytes // 64))
                 ref = None
                 for vname, fn, weights, nbytes in variants:
                     o = fn(weights[0]).float().clone()
@@ -129,7 +137,7 @@ def main():
                                       "max_us": round(max(us), 2), "weight_bytes": nbytes,
                                       "weight_bytes_per_s": round(nbytes / (med * 1e-6)),
                                       "max_diff_vs_first": round((o - ref).abs().max().item(), 5)}), flush=True)
-            del ws, qs
+            del ws, qs, q4s
 
 
 if __name__ == "__main__":

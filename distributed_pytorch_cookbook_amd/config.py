@@ -89,9 +89,10 @@ def build_parser(recipe: str = "single") -> argparse.ArgumentParser:
     p.add_argument("--kv_cache_dtype", type=str, default="bf16", choices=["bf16", "fp8"],
                    help="KV cache of the end-of-epoch samples: the compute dtype, or 1-byte e4m3 (GPU, bf16, "
                         "head_dim 32 / 64 / 128)")
-    p.add_argument("--decode_weight_dtype", type=str, default="bf16", choices=["bf16", "fp8"],
-                   help="Linear weights of the end-of-epoch samples' one-token steps: the compute dtype, or an e4m3 "
-                        "copy with one scale per output row, made for each sampling (GPU, bf16, non-sharded)")
+    p.add_argument("--decode_weight_dtype", type=str, default="bf16", choices=["bf16", "fp8", "fp4"],
+                   help="Linear weights of the end-of-epoch samples' one-token steps: the compute dtype, an e4m3 "
+                        "copy with one scale per output row, or an MXFP4 copy (e2m1, one power-of-two scale per "
+                        "32 k), made for each sampling (GPU, bf16, non-sharded)")
     p.add_argument("--bucket_mb", type=float, default=128.0, help="DDP gradient bucket size")
     p.add_argument("--reduce_dtype", type=str, default="fp32", choices=["fp32", "bf16"])
     p.add_argument("--no_overlap", action="store_true", help="all-reduce after backward instead of during")

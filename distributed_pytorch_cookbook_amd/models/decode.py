@@ -84,23 +84,25 @@ class KVCache:
         return self.len_t.view(N, 1) if self.ragged else self.len_t.expand(N, 1)
 
 
-class Fp8DecodeStore:
-    """The model's parameter store with an fp8 (e4m3, one f32 scale per output row) copy of the
-    Linear weights a one-token step streams: each layer's fused QKV, ``to_out``, ``up_proj`` and
-    ``down_proj`` and the LM head, as ``ops/gemm.py:QWeight`` -- ``linear_fwd`` then runs
-    ``dpc_gemm_wq8`` (csrc/wq_gemm.hip).  LayerNorm weights, biases and embeddings are the wrapped
-    store's, as is everything else.  The copy is extra memory beside the bf16 weights (prefill and
-    blocks of tokens keep those: about 1.6 GB for GPT-2 XL), and a snapshot: it does not follow
-    later updates of the weights."""
+class QuantDecodeStore:
+    """The model's parameter store with a quantised copy of the Linear weights a one-token step
+    streams: each layer's fused QKV, ``to_out``, ``up_proj`` and ``down_proj`` and the LM head.
+    ``dtype="fp8"``: e4m3 with one f32 scale per output row, as ``ops/gemm.py:QWeight`` --
+    ``linear_fwd`` then runs ``dpc_gemm_wq8`` (csrc/wq_gemm.hip); ``"fp4"``: MXFP4, as
+    ``ops/gemm.py:MxWeight`` -- ``dpc_gemm_wq4`` (csrc/wq4_gemm.hip).  LayerNorm weights, biases and
+    embeddings are the wrapped store's, as is everything else.  The copy is extra memory beside the
+    bf16 weights (prefill and blocks of tokens keep those: about 1.6 GB for GPT-2 XL in fp8, 0.8 GB
+    in fp4), and a snapshot: it does not follow later updates of the weights."""
 
-    def __init__(self, model, store):
+    def __init__(self, model, store, dtype="fp8"):
         self._store = store
+        self.dtype = dtype
         self._q, self._qkv = {}, {}
         for layer in model.decoder.layers:
-            self._qkv[id(layer.attn)] = quantize_weight(_qkv_weight(store, layer.attn))
+            self._qkv[id(layer.attn)] = quantize_weight(_qkv_weight(store, layer.attn), dtype)
             for lin in (layer.attn.to_out, layer.fc.up_proj, layer.fc.down_proj):
-                self._q[id(lin.weight)] = quantize_weight(store.weight(lin.weight))
-        self._q[id(model.lm_head.weight)] = quantize_weight(store.weight(model.lm_head.weight))
+                self._q[id(lin.weight)] = quantize_weight(store.weight(lin.weight), dtype)
+        self._q[id(model.lm_head.weight)] = quantize_weight(store.weight(model.lm_head.weight), dtype)
 
     def weight(self, p):
         q = self._q.get(id(p))
@@ -113,23 +115,28 @@ class Fp8DecodeStore:
         return getattr(self._store, name)
 
 
-def quantize_decode_weights(model) -> Fp8DecodeStore:
-    """An ``Fp8DecodeStore`` of the model's weights as they are now, for ``decode_step`` /
-    ``GraphDecoder`` / ``model.decode(..., weights=)``.  Needs CUDA and a bf16 non-sharded store
-    (``ValueError`` otherwise); the step takes at most 64 sequences."""
+Fp8DecodeStore = QuantDecodeStore  # (its name while fp8 was the only dtype)
+
+
+def quantize_decode_weights(model, dtype="fp8") -> QuantDecodeStore:
+    """A ``QuantDecodeStore`` (``dtype`` "fp8" or "fp4") of the model's weights as they are now, for
+    ``decode_step`` / ``GraphDecoder`` / ``model.decode(..., weights=)``.  Needs CUDA and a bf16
+    non-sharded store (``ValueError`` otherwise); the step takes at most 64 sequences."""
+    if dtype not in ("fp8", "fp4"):
+        raise ValueError(f"quantised decode weights: dtype must be 'fp8' or 'fp4', not {dtype!r}")
     from ..parallel.store import LocalStore
 
     store = ensure_store(model)
     device = next(model.parameters()).device
     if device.type != "cuda" or not isinstance(store, LocalStore) or store.compute_dtype != torch.bfloat16:
-        raise ValueError("fp8 decode weights: need CUDA and a bf16 non-sharded parameter store "
+        raise ValueError(f"{dtype} decode weights: need CUDA and a bf16 non-sharded parameter store "
                          f"(device {device}, {type(store).__name__} {store.compute_dtype})")
-    return Fp8DecodeStore(model, store)
+    return QuantDecodeStore(model, store, dtype)
 
 
 def check_fp8_weight_batch(N: int) -> None:
     if N > _SKINNY_MAX_ROWS:
-        raise ValueError(f"fp8 decode weights: a batch of at most {_SKINNY_MAX_ROWS} sequences, not {N}")
+        raise ValueError(f"fp8 / fp4 decode weights: a batch of at most {_SKINNY_MAX_ROWS} sequences, not {N}")
 
 
 def _block_attend(qkv, cache, li, H, hd):
@@ -265,7 +272,7 @@ def kv_decode_forward(model, input_ids, position_ids, cache, lens=None, prefill_
     ``prefill_chunk``: with an empty cache and ``0 < prefill_chunk < n``, the prompt runs in
     blocks of that many tokens (``prefill_chunked``).
 
-    ``weights``: an ``Fp8DecodeStore`` (``quantize_decode_weights``) for the one-token step; the
+    ``weights``: a ``QuantDecodeStore`` (``quantize_decode_weights``) for the one-token step; the
     prompt and blocks of tokens run on the bf16 weights."""
     store = ensure_store(model)
     N, n = input_ids.shape
@@ -323,7 +330,7 @@ class GraphDecoder:
     next token straight into the graph's own ``tok`` buffer and into its column of the output
     buffer, and advances the lengths: a replay then needs nothing from the host, ``step()`` with
     no argument.  Needs a non-sharded parameter store (single GPU / DDP); FSDP decodes eagerly.
-    ``weights``: an ``Fp8DecodeStore`` (``quantize_decode_weights``) to run the step's Linears on."""
+    ``weights``: a ``QuantDecodeStore`` (``quantize_decode_weights``) to run the step's Linears on."""
 
     def __init__(self, model, cache, sampler=None, weights=None):
         self.model, self.cache, self.sampler = model, cache, sampler

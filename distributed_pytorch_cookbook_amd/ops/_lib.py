@@ -275,6 +275,17 @@ class WqArgs(ctypes.Structure):
     ]
 
 
+class Wq4Args(ctypes.Structure):
+    """``wq4_gemm.hip:Wq4Args``: WqArgs with MXFP4 weight bytes ``q`` (``ldw`` in bytes) and their e8m0
+    block ``scale`` [Nw, K / 32]."""
+    _fields_ = WqArgs._fields_
+
+
+class Wq4QuantArgs(ctypes.Structure):
+    """``wq4_gemm.hip:Wq4QuantArgs``."""
+    _fields_ = [("w", P), ("q", P), ("scale", P), ("ldw", LL), ("ldq", LL), ("N", c_int), ("K", c_int)]
+
+
 class LnLinearArgs(ctypes.Structure):
     """``ln_linear.hip:LnLinearArgs``: f32 ``x`` normalised by ``gamma`` / ``beta`` / ``eps`` on its way
     into a SkinnyArgs (``scale`` null) or WqArgs (``scale`` set) product."""
@@ -302,6 +313,8 @@ _FUNCS = {
     "dpc_gemm_skinny": SkinnyArgs,
     "dpc_gemm_wq8": WqArgs,
     "dpc_wq_quantize": WqQuantArgs,
+    "dpc_gemm_wq4": Wq4Args,
+    "dpc_wq4_quantize": Wq4QuantArgs,
     "dpc_ln_linear": LnLinearArgs,
     "dpc_sample": SampleArgs,
     "dpc_embedding_bwd_sorted": EmbBwdArgs,

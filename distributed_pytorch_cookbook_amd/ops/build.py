@@ -31,8 +31,8 @@ ARCH = os.environ.get("DPC_OFFLOAD_ARCH", "gfx950")
 # gemm7_part*.hip: the persistent GEMM kernels' instantiations, dealt over several files that
 # compile in parallel (ops/gen_gemm_parts.py; gemm.hip holds the dispatcher and the v1-v3 kernels)
 SOURCES = ["gemm.hip", "gemm_f32.hip", "attention.hip", "attention_f32.hip", "layernorm.hip", "misc.hip",
-           "decode.hip", "decode_split.hip", "append_attn.hip", "skinny_gemm.hip", "wq_gemm.hip", "ln_linear.hip", "sample.hip", "embed_bwd.hip", "ipc_coll.hip"] + sorted(p.name for p in CSRC.glob("gemm7_part*.hip"))
-HEADERS = ["common.h", "fp8.h", "gemm.h", "gemm_plan.h", "gemm7_kern.h", "gemm9_kern.h", "gemm7_extern.inc"]
+           "decode.hip", "decode_split.hip", "append_attn.hip", "skinny_gemm.hip", "wq_gemm.hip", "wq4_gemm.hip", "ln_linear.hip", "sample.hip", "embed_bwd.hip", "ipc_coll.hip"] + sorted(p.name for p in CSRC.glob("gemm7_part*.hip"))
+HEADERS = ["common.h", "fp8.h", "mxfp4.h", "gemm.h", "gemm_plan.h", "gemm7_kern.h", "gemm9_kern.h", "gemm7_extern.inc"]
 
 # code-object v5 keeps the library loadable by torch's bundled ROCm 7.0 runtime as
 # well as by the 7.2 toolchain in /opt/rocm.
@@ -60,13 +60,14 @@ def hipcc() -> str:
 # into v_pk_add_f32 fed by v_mov_b32 pairs (32 moves + 13 packed adds per tile instead of 32
 # adds) and the dS products into v_pk_mul_f32; packed f32 VALU beside MFMAs costs extra issue
 # cycles (MI355X_MICROARCH.md: "an anti-lever beside MFMAs")
-# decode_split.hip, append_attn.hip, skinny_gemm.hip, wq_gemm.hip, ln_linear.hip: no packed-f32 VALU (the accumulator updates
+# decode_split.hip, append_attn.hip, skinny_gemm.hip, wq_gemm.hip, wq4_gemm.hip, ln_linear.hip: no packed-f32 VALU (the accumulator updates
 # and epilogue math stay plain v_fma_f32 / v_mul_f32 / v_add_f32); the e4m3 KV-cache kernels live in
 # decode_split.hip and append_attn.hip (fp8.h) and are built with the same flags
 NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"attention.hip": ["-fno-honor-nans", "-fno-slp-vectorize"], "attention_f32.hip": ["-fno-honor-nans"],
               "decode_split.hip": NO_PACKED_F32, "append_attn.hip": NO_PACKED_F32,
-              "skinny_gemm.hip": NO_PACKED_F32, "wq_gemm.hip": NO_PACKED_F32, "ln_linear.hip": NO_PACKED_F32}
+              "skinny_gemm.hip": NO_PACKED_F32, "wq_gemm.hip": NO_PACKED_F32, "wq4_gemm.hip": NO_PACKED_F32,
+              "ln_linear.hip": NO_PACKED_F32}
 
 
 HASH_PATH = LIB_PATH.with_suffix(".so.srchash")

@@ -407,7 +407,8 @@ def linear_fwd(x, w, *, bias=None, act=None, residual=None, aux_out=None, out=No
     """y = act(x @ w^T + bias) (+ residual); x [M, K], w [N, K] (nn.Linear layout).
     ``aux_out`` receives the pre-activation, or act'(pre-activation) with ``aux_deriv``.
     ``w`` a ``QWeight`` (fp8 weight bytes and per-row scales): ``dpc_gemm_wq8`` for up to 64 rows,
-    ``ValueError`` for anything that kernel does not take.
+    ``ValueError`` for anything that kernel does not take; an ``MxWeight`` (MXFP4 bytes and block
+    scales): ``dpc_gemm_wq4`` on the same terms, and no ``norm=``.
     ``norm=(gamma, beta, eps)``: x is the f32 residual stream and the product takes
     bf16(LayerNorm(x)) in the same launch (``dpc_ln_linear``, w bf16 or a ``QWeight``); operands
     that kernel does not take (``ln_linear_ok``) are a ``ValueError``, never two launches."""
@@ -419,6 +420,10 @@ def linear_fwd(x, w, *, bias=None, act=None, residual=None, aux_out=None, out=No
         if aux_out is not None:
             raise ValueError("linear_fwd (fp8 weights): no aux_out")
         return _linear_fwd_wq8(x, w, bias, act_code(act), residual, out, out_dtype)
+    if isinstance(w, MxWeight):
+        if aux_out is not None:
+            raise ValueError("linear_fwd (fp4 weights): no aux_out")
+        return _linear_fwd_wq4(x, w, bias, act_code(act), residual, out, out_dtype)
     if x.is_cuda and aux_out is None and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16:
         M = x.shape[0]
         if M <= _GEMV_ROWS:
@@ -565,9 +570,8 @@ def weight_quantize_ref(w: torch.Tensor, inv: torch.Tensor) -> torch.Tensor:
     return (w.float() * inv[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)
 
 
-def quantize_weight(w: torch.Tensor) -> QWeight:
-    """``w`` [N, K] bf16 on the GPU (K % 16 == 0, rows 16-B aligned) as a ``QWeight``: the scales by
-    torch (set-up, once per weight), the bytes by ``dpc_wq_quantize``."""
+def _quantize_weight_fp8(w: torch.Tensor) -> QWeight:
+    """``quantize_weight`` (below) with its default ``dtype="fp8"``."""
     if not (w.dim() == 2 and w.is_cuda and w.dtype == torch.bfloat16 and w.stride(1) == 1 and w.shape[1] % 16 == 0
             and w.shape[0] > 0 and w.stride(0) % 8 == 0 and w.stride(0) >= w.shape[1] and w.data_ptr() % 16 == 0):
         raise ValueError("quantize_weight: a CUDA bf16 [N, K] weight with K % 16 == 0 and 16-B aligned rows")
@@ -613,6 +617,121 @@ def _linear_fwd_wq8(x, w, bias, act, residual, out, out_dtype, plan=None):
         ldr=residual.stride(0) if residual is not None else 0, ldy=out.stride(0),
         M=M, N=N, Nw=Nw, K=K, act=act, y_f32=int(out.dtype == torch.float32), nb=nb, nw=nw)
     _lib.call("dpc_gemm_wq8", args, x.device)
+    return out
+
+
+# Weight-only MXFP4 Linears of the decode step (csrc/wq4_gemm.hip): the weight stream at half a byte
+# per element.  OCP MXFP4: e2m1 elements (0, .5, 1, 1.5, 2, 3, 4, 6 and a sign), two per byte, and one
+# e8m0 scale byte, 2^(byte - 127), per block of 32 consecutive k of a row.  mx_quantize_ref below is
+# the definition of the format.  The kernel turns each byte and its block's scale into two bf16 by
+# one convert, exactly, and runs the bf16 MFMA: activations are not quantised and no scale meets
+# the accumulator.  dpc_gemm_wq4 takes every row count 1..64 and every width: there is no other
+# path behind an MxWeight.
+MX_BLOCK = 32
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+_E2M1_STEPS = ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False), (3.5, True), (5.0, False))
+
+
+class MxWeight:
+    """An MXFP4 weight: ``q`` [N, K / 2] uint8 (element 2j in the low nibble of byte j), ``scale``
+    [N, K / 32] uint8 (e8m0), ``shape`` (N, K); w ~ ``mx_dequantize(q, scale)``."""
+    __slots__ = ("q", "scale", "shape")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        if (q.dim() != 2 or q.dtype != torch.uint8 or scale.dtype != torch.uint8 or q.shape[1] % (MX_BLOCK // 2)
+                or scale.shape != (q.shape[0], q.shape[1] // (MX_BLOCK // 2))):
+            raise ValueError("MxWeight: q [N, K / 2] uint8 and scale [N, K / 32] uint8, K % 32 == 0")
+        self.q, self.scale, self.shape = q, scale, torch.Size((q.shape[0], 2 * q.shape[1]))
+
+
+def mx_quantize_ref(w: torch.Tensor):
+    """(q [N, K / 2] uint8, scale [N, K / 32] uint8) of a finite ``w`` [N, K], K % 32 == 0: the
+    definition of the format and the torch twin of ``dpc_wq4_quantize``, bit for bit.  Per block of
+    32 consecutive k of a row: the exponent e is the smallest integer with 6 * 2^e >= amax, read off
+    frexp(amax) = (m, x) as x - 3 for m <= .75, else x - 2, clamped to [-125, 125] (every
+    dequantised value is then a finite, normal bf16), 0 for a block of zeros; the scale byte is
+    e + 127.  |w| * 2^-e is rounded to the nearest of the e2m1 magnitudes, ties to the even code
+    (the compares of ``_E2M1_STEPS``), and saturates at 6 -- which only the upper clamp can reach;
+    the sign goes in bit 3.  Element 2j sits in the low nibble of byte j, the order in which
+    v_cvt_scalef32_pk_bf16_fp4's byte selector yields ascending k."""
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"mx_quantize_ref: K % {MX_BLOCK} == 0, not K = {K}")
+    f = w.float().reshape(N, K // MX_BLOCK, MX_BLOCK)
+    amax = f.abs().amax(dim=2)
+    m, x = torch.frexp(amax)
+    e = torch.where(amax > 0, x - torch.where(m <= 0.75, 3, 2), torch.zeros_like(x)).clamp(-125, 125)
+    v = f.abs() * ((127 - e) << 23).to(torch.int32).view(torch.float32)[:, :, None]  # * 2^-e, exact
+    code = torch.zeros_like(v, dtype=torch.int32)
+    for t, closed in _E2M1_STEPS:
+        code += (v >= t) if closed else (v > t)
+    code = (code | (torch.signbit(f).to(torch.int32) << 3)).view(N, K // 2, 2)
+    return (code[:, :, 0] | (code[:, :, 1] << 4)).to(torch.uint8), (e + 127).to(torch.uint8)
+
+
+def mx_dequantize(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """[N, K] f32 of an MXFP4 weight: sign * e2m1 magnitude * 2^(scale - 127), exact."""
+    N = q.shape[0]
+    code = torch.stack((q & 0xF, q >> 4), dim=2).view(N, -1).long()
+    mag = torch.tensor(_E2M1, device=q.device)[code & 7] * (1.0 - 2.0 * (code >> 3))
+    s = (scale.to(torch.int32) << 23).view(torch.float32)
+    return (mag.view(N, -1, MX_BLOCK) * s[:, :, None]).view(N, -1)
+
+
+def quantize_weight(w: torch.Tensor, dtype: str = "fp8"):
+    """``w`` [N, K] bf16 on the GPU with 16-B aligned rows, quantised for the few-row Linears.
+    ``dtype="fp8"`` (K % 16 == 0): a ``QWeight``, the scales by torch (set-up, once per weight), the
+    bytes by ``dpc_wq_quantize``.  ``dtype="fp4"`` (K % 32 == 0): an ``MxWeight``, codes and scales by
+    ``dpc_wq4_quantize``."""
+    if dtype == "fp8":
+        return _quantize_weight_fp8(w)
+    if dtype != "fp4":
+        raise ValueError(f"quantize_weight: dtype must be 'fp8' or 'fp4', not {dtype!r}")
+    if not (w.dim() == 2 and w.is_cuda and w.dtype == torch.bfloat16 and w.stride(1) == 1 and w.shape[1] % MX_BLOCK == 0
+            and w.shape[0] > 0 and w.stride(0) % 8 == 0 and w.stride(0) >= w.shape[1] and w.data_ptr() % 16 == 0):
+        raise ValueError("quantize_weight: a CUDA bf16 [N, K] weight with K % 32 == 0 and 16-B aligned rows")
+    N, K = w.shape
+    q = torch.empty(N, K // 2, device=w.device, dtype=torch.uint8)
+    scale = torch.empty(N, K // MX_BLOCK, device=w.device, dtype=torch.uint8)
+    _lib.call("dpc_wq4_quantize", _lib.Wq4QuantArgs(w=w.data_ptr(), q=q.data_ptr(), scale=scale.data_ptr(),
+                                                    ldw=w.stride(0), ldq=K // 2, N=N, K=K), w.device)
+    return MxWeight(q, scale)
+
+
+def _wq4_ok(x, w, bias, residual, out):
+    q, K = w.q, w.shape[1]
+    return (x.dim() == 2 and out.dim() == 2 and x.is_cuda and q.is_cuda and x.dtype == torch.bfloat16
+            and x.shape[1] == K and out.shape[0] == x.shape[0]
+            and out.dtype in (torch.float32, torch.bfloat16) and x.stride(1) == 1 and q.stride(1) == 1
+            and x.stride(0) % 8 == 0 and x.stride(0) >= K and q.stride(0) % 16 == 0
+            and x.data_ptr() % 16 == 0 and q.data_ptr() % 16 == 0
+            and w.scale.is_cuda and w.scale.is_contiguous()
+            and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() >= q.shape[0]))
+            and (residual is None or (residual.dtype == torch.float32 and residual.stride(1) == 1
+                                      and residual.shape[0] >= x.shape[0] and residual.shape[1] >= q.shape[0]))
+            and out.stride(1) == 1 and 0 < q.shape[0] <= out.shape[1])
+
+
+def _linear_fwd_wq4(x, w, bias, act, residual, out, out_dtype, plan=None):
+    """``dpc_gemm_wq4`` (csrc/wq4_gemm.hip) on an ``MxWeight``; operands the kernel does not take
+    raise.  The plan is ``skinny_plan``'s, or ``plan``: one of SKINNY_PLANS (tests, measurements)."""
+    M = x.shape[0]
+    Nw, K = w.shape
+    if M > _SKINNY_MAX_ROWS:
+        raise ValueError(f"linear_fwd (fp4 weights): at most {_SKINNY_MAX_ROWS} rows, not {M}")
+    if out is None:
+        out = torch.empty(M, Nw, device=x.device, dtype=out_dtype)
+    if not (M > 0 and _wq4_ok(x, w, bias, residual, out)):
+        raise ValueError("linear_fwd (fp4 weights): operands the kernel does not take (CUDA bf16 x [M, K] with the "
+                         "weight's K, 16-B aligned rows, f32 bias / residual)")
+    N = out.shape[1]
+    nb, nw = plan or skinny_plan(M, N, K, torch.cuda.get_device_properties(x.device).multi_processor_count)
+    args = _lib.Wq4Args(
+        x=x.data_ptr(), q=w.q.data_ptr(), scale=w.scale.data_ptr(), bias=_lib.ptr(bias), residual=_lib.ptr(residual),
+        y=out.data_ptr(), ldx=x.stride(0), ldw=w.q.stride(0),
+        ldr=residual.stride(0) if residual is not None else 0, ldy=out.stride(0),
+        M=M, N=N, Nw=Nw, K=K, act=act, y_f32=int(out.dtype == torch.float32), nb=nb, nw=nw)
+    _lib.call("dpc_gemm_wq4", args, x.device)
     return out
 
 

@@ -53,7 +53,7 @@ def generate(model, prompt: str, tokenizer, device, max_new_tokens: int = 20, us
     """``prefill_chunk``: the KV-cache decode takes a prompt longer than that in blocks of that many
     tokens (0: in one).  ``kv_dtype``: "fp8" for the 1-byte KV cache (``new_kv_cache``); a model
     without ``decode`` ignores it, as it ignores the cache.  ``weight_dtype``: "fp8" runs the
-    one-token steps on an e4m3 copy of the Linear weights, made for this call
+    one-token steps on an e4m3 copy of the Linear weights, "fp4" on an MXFP4 copy, made for this call
     (``models/decode.py:quantize_decode_weights``: CUDA, a bf16 non-sharded store)."""
     if temperature > 0 or top_k > 0 or top_p < 1.0:  # sampling: the batched loop with one prompt
         return generate_batch(model, [prompt], tokenizer, device, max_new_tokens, temperature, top_k, top_p, seed,
@@ -77,16 +77,17 @@ def _kv_kw(kv_dtype):
 
 
 def _decode_weights(model, weight_dtype, N):
-    """The one-token steps' weights: None for the store's own, or an fp8 copy of them as they are
-    now -- made per call, never kept: the recipes sample between epochs of training."""
+    """The one-token steps' weights: None for the store's own, or an fp8 (e4m3) or fp4 (MXFP4) copy
+    of them as they are now -- made per call, never kept: the recipes sample between epochs of
+    training."""
     if weight_dtype in (None, "bf16"):
         return None
-    if weight_dtype != "fp8":
-        raise ValueError(f"weight_dtype must be None, 'bf16' or 'fp8', not {weight_dtype!r}")
+    if weight_dtype not in ("fp8", "fp4"):
+        raise ValueError(f"weight_dtype must be None, 'bf16', 'fp8' or 'fp4', not {weight_dtype!r}")
     from ..models.decode import check_fp8_weight_batch, quantize_decode_weights
 
     check_fp8_weight_batch(N)
-    return quantize_decode_weights(model)
+    return quantize_decode_weights(model, weight_dtype)
 
 
 def _generate_cached(model, input_ids, tokenizer, device, max_new_tokens, prefill_chunk=0, kv_dtype=None,
@@ -158,7 +159,7 @@ def generate_batch(model, prompts, tokenizer, device, max_new_tokens: int = 20, 
     ``sample_uniform(seed, n, step)``: the same arguments give the same text, on every rank).
     ``prefill_chunk``: the padded prompts go into the cache in blocks of that many tokens (0: in one).
     ``kv_dtype``: "fp8" for the 1-byte KV cache (ignored without ``decode``).  ``weight_dtype``: "fp8"
-    for the one-token steps on e4m3 weights, as in ``generate`` (at most 64 prompts)."""
+    or "fp4" for the one-token steps on e4m3 or MXFP4 weights, as in ``generate`` (at most 64 prompts)."""
     from ..ops.sample import Sampler
 
     device = torch.device(device)
