@@ -16,15 +16,18 @@ with one f32 accumulator, were 1e-5 to 4e-5 off.  It costs the f32 forward about
 (tests/test_attention_scores_gpu.py and csrc/attention_f32.hip have the measurements).
 The backward forms P from f32-accumulated scores; its gradients are held to 1e-4.
 
-HIP path (bf16, head_dim 32, 64 or 128 natively): ``dpc_attn_fwd`` / ``dpc_attn_bwd`` flash
-kernels (``csrc/attention.hip``) -- O(S) memory, f32 log-sum-exp saved for the backward.
+HIP path (bf16, head_dim 32, 64, 128 or 256 natively): ``dpc_attn_fwd`` / ``dpc_attn_bwd`` flash
+kernels (``csrc/attention.hip``; 256 has kernels of its own there) -- O(S) memory, f32
+log-sum-exp saved for the backward.
 f32 operands (``--disable_amp``) run ``dpc_attn_fwd_f32`` / ``dpc_attn_bwd_f32``
-(``csrc/attention_f32.hip``, f32 matrix cores), also O(S).
+(``csrc/attention_f32.hip``, f32 matrix cores; head_dim 32, 64 or 128), also O(S).
 head_dim 32 is the reference default config (``/root/reference/main-single.py:160``); other
-head sizes up to 128 are zero-padded to the next kernel size on the way in (16 -> 32, 48 -> 64,
-96 -> 128).  The reference's ``SelfAttention`` takes any ``--head_dim``
-(``/root/reference/models/gpt.py:44-66``): sizes above 128 run the reference math on the
-device (O(S^2) memory, correct but slow) rather than refusing.
+head sizes up to the dtype's largest kernel are zero-padded to the next kernel size on the way
+in (16 -> 32, 48 -> 64, 96 -> 128, and for bf16 160 -> 256; the scale is the true head_dim's).
+The reference's ``SelfAttention`` takes any ``--head_dim``
+(``/root/reference/models/gpt.py:44-66``): bf16 sizes above 256 and f32 sizes above 128 run the
+reference math on the device (O(S^2) memory, correct but slow) rather than refusing.
+The fp8 KV cache and ``append_attention`` have kernels at 32, 64 and 128 only (``HD_KERNELS``).
 CPU / fp32 path: the same math with torch ops (test oracle).
 """
 from __future__ import annotations
@@ -36,14 +39,16 @@ import torch
 
 from . import _lib
 
-HD_KERNELS = (32, 64, 128)
+HD_KERNELS = (32, 64, 128)  # every dtype and kernel family: f32, the fp8 cache, append attention
 HD_KERNEL = 128  # the largest
+HD_KERNELS_BF16 = HD_KERNELS + (256,)  # the bf16 flash forward / backward only
 
 
-def kernel_head_dim(head_dim: int) -> int | None:
-    """The kernel size a head of ``head_dim`` runs at (itself for 32 / 64 / 128, else padded
-    up); None above the largest kernel (the device then runs the reference math)."""
-    for k in HD_KERNELS:
+def kernel_head_dim(head_dim: int, dtype: torch.dtype | None = None) -> int | None:
+    """The kernel size a head of ``head_dim`` runs at (itself for 32 / 64 / 128, and 256 for
+    bf16; else padded up); None above the largest kernel of ``dtype`` (the device then runs the
+    reference math)."""
+    for k in (HD_KERNELS_BF16 if dtype == torch.bfloat16 else HD_KERNELS):
         if head_dim <= k:
             return k
     return None
@@ -51,8 +56,8 @@ def kernel_head_dim(head_dim: int) -> int | None:
 
 def _use_hip(t: torch.Tensor, head_dim: int | None = None) -> bool:
     """bf16 -> csrc/attention.hip; f32 (--disable_amp) -> csrc/attention_f32.hip; head sizes
-    past the largest kernel -> the reference math (on whatever device ``t`` is on)."""
-    if head_dim is not None and kernel_head_dim(head_dim) is None:
+    past the dtype's largest kernel -> the reference math (on whatever device ``t`` is on)."""
+    if head_dim is not None and kernel_head_dim(head_dim, t.dtype) is None:
         return False
     return t.is_cuda and t.dtype in (torch.bfloat16, torch.float32)
 
@@ -119,7 +124,7 @@ def attention_fwd(qkv: torch.Tensor, N: int, S: int, heads: int, head_dim: int,
             o = out
         return o, lse
     scale = 1.0 / math.sqrt(head_dim)
-    kd = kernel_head_dim(head_dim)
+    kd = kernel_head_dim(head_dim, qkv.dtype)
     if head_dim != kd:
         q, k, v = split_qkv(qkv, heads, head_dim)
         qkv_p = torch.cat([_pad_heads(t, T, heads, head_dim, kd) for t in (q, k, v)], dim=1)
@@ -179,7 +184,7 @@ def attention_bwd(dout: torch.Tensor, qkv: torch.Tensor, o: torch.Tensor, lse: t
             return dqkv
         return g.to(qkv.dtype)
     scale = 1.0 / math.sqrt(head_dim)
-    kd = kernel_head_dim(head_dim)
+    kd = kernel_head_dim(head_dim, qkv.dtype)
     if head_dim != kd:
         q, k, v = split_qkv(qkv, heads, head_dim)
         qkv_p = torch.cat([_pad_heads(t, T, heads, head_dim, kd) for t in (q, k, v)], dim=1)

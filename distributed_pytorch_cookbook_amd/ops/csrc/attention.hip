@@ -1,5 +1,6 @@
 // Flash attention (forward + backward) for gfx950: head_dim 32, 64 or 128 natively (template HD),
-// bf16 in / bf16 out, f32 online softmax, causal + optional key-padding mask.
+// bf16 in / bf16 out, f32 online softmax, causal + optional key-padding mask.  head_dim 256 has
+// kernels of its own (namespace hd256, ahead of the launchers; its header has their design).
 //
 // Replaces the reference's materialised attention (/root/reference/models/gpt.py:75-100: q@k,
 // host-built causal mask copied H2D every layer, masked_fill, fp32 softmax, @v, head merge)
@@ -52,7 +53,7 @@ struct AttnArgs {
   int N, S, H;
   float scale;
   int causal;
-  int hd;                                       // head_dim: 32, 64 or 128
+  int hd;                                       // head_dim: 32, 64, 128 or 256
   int order;                                    // backward block order (set by the launcher: DPC_ATTN_ORDER)
 };
 
@@ -1406,6 +1407,500 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(AttnArgs p) {
   }
 }
 
+// ------------------------------------------------------------------ head_dim 256
+// Forward, dQ and dK / dV kernels of their own: the kernels above do not stretch to 256 (their
+// 4-slot ring of K|V pairs would be 256 KiB of LDS, the dK / dV kernel's K, V, dK^T, dV^T 384
+// registers before any score, and aswz() maps 16 consecutive 512-B rows onto 4 chunk slots).
+// Same contract (AttnArgs), same orientations (query on the lane in the forward and dQ, key on
+// the lane in dK / dV), same 64-row tiles and lazy rescale, one workgroup of 4 waves per CU.
+//
+// LDS: a 2-slot ring of pairs (K|V, or Q|dO), 2 x 2 x 32 KiB = 128 KiB of the 160, one tile
+//   ahead: at the top of tile t every wave waits for its own pieces of tile t (vmcnt(0)), the
+//   barrier makes that every wave's and frees tile t-1's slot, and tile t+1's DMA is issued into
+//   it before tile t's math.  Chosen over 32-row tiles in 4 slots (half the keys per barrier and
+//   per softmax update, and tests/attn_cases.py describes 64-key tiles) and over separate K and V
+//   rings (two waits and two barriers per tile for the same 128 KiB): a whole tile of MFMA work
+//   (64 to 96 MFMAs per wave) covers one pair's DMA.  The dK / dV kernel adds 1 KiB of lse / delta rows.
+// Swizzle: a row is 32 chunks of 16 B; chunk c of row r sits at chunk c ^ swz(r), swz(r) = the
+//   two 2-bit halves of r & 15 swapped.  LDS has 64 dword banks = 16 chunk slots (address mod 256 B).
+//   ds_read_b128 row reads: 16 consecutive lanes read one chunk of 16 consecutive rows; swz is a
+//   bijection of r & 15, so they take 16 different slots.  ds_read_b64_tr_b16 column reads: 32
+//   consecutive lanes read 4 consecutive chunks (4-aligned) of rows 4 a .. 4 a + 3: the chunk's low
+//   two bits meet the constant r >> 2, its next two bits meet r & 3, so the 16 (row, chunk) pairs
+//   take 16 different slots (the two 8-B halves of a chunk are different banks).  Derived, under
+//   that lane grouping; no bank-conflict counter has been read for it.
+//   The DMA writes lane-linearly (one instruction = 2 rows), so the swizzle is applied to the
+//   source address, as above.
+// Registers (512 per lane): forward Q 64 + O^T 128 + S^T 32; dQ Q 64 + dO 64 + dQ^T 128 + S^T /
+//   dP^T 32.  dK / dV sweeps its queries TWICE: pass 0 forms P and dV^T (K 64 + dV^T 128), pass 1
+//   forms P, dP, dS and dK^T (K 64 + V 64 + dK^T 128), one 128-register accumulator serving both
+//   (80 MFMAs per 32-query sub-block against 64 with all 384 registers resident, which leaves
+//   no room for S, dP and the operands without scratch).
+//   hipcc -Rpass-analysis=kernel-resource-usage, gfx950:          VGPR  AGPR  LDS [B]  scratch
+//     attn256_fwd_kernel                                            256   209   131072     0
+//     attn256_bwd_dq_kernel                                         248   256   131072     0
+//     attn256_bwd_dkdv_kernel                                       256   177   132096     0
+//   (the sched_barriers keep a sub-block's LDS reads from being hoisted over the one before; the
+//   masks use 32-bit compile-time key offsets -- as 64-bit lane-variable shifts hipcc hoisted 32
+//   two-register masks out of the tile loop and spilled them)
+namespace hd256 {
+constexpr int HD = 256;
+constexpr int TILE = KT * HD;  // elements of one 64-row tile (32 KiB)
+constexpr int NPW = 8;         // 1-KiB DMA pieces per wave per tile
+constexpr int NST = 16;        // k-steps of a product over head_dim
+constexpr int NDT = 8;         // 32-column blocks of an HD-wide accumulator
+constexpr int PAIR = 2 * TILE;
+
+__device__ __forceinline__ int swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+// element offset of (row, 16-B chunk) in the LDS image of a tile
+__device__ __forceinline__ int toff(int row, int chunk) { return row * HD + ((chunk ^ swz(row)) << 3); }
+
+// piece g (wave wid, instruction i: g = wid * NPW + i) fills rows 2 g, 2 g + 1: lane l writes chunk
+// slot l & 31 of row 2 g + (l >> 5) and fetches the logical chunk that the swizzle maps there
+__device__ __forceinline__ void dma_voff(int (&v)[NPW], long long ld, int wid, int lane) {
+#pragma unroll
+  for (int i = 0; i < NPW; ++i) {
+    const int row = 2 * (wid * NPW + i) + (lane >> 5);
+    v[i] = (int)((long long)row * ld * 2 + (((lane & 31) ^ swz(row)) << 4));
+  }
+}
+// one 64-row tile (rows >= S, or the whole tile if !valid, land as zeros)
+__device__ __forceinline__ void tile_dma(const bf16_t* base, long long ld, int row0, int S, bool valid,
+                                         const int (&v)[NPW], bf16_t* lds, int wid) {
+  const __amdgpu_buffer_rsrc_t rs = rows_rsrc(base, (unsigned)(ld * 2), row0, S, valid);
+#pragma unroll
+  for (int i = 0; i < NPW; ++i) dma16(rs, v[i], lds + (wid * NPW + i) * 512);
+}
+// row_frag / tr_frag of the kernels above on this image.  The image is addressed through 32-bit
+// LDS pointers: with generic pointers hipcc kept the loop-invariant element offsets as 64-bit
+// values, 2 registers each, and spilled some of them.
+typedef const bf16_t __attribute__((address_space(3))) * ldsp_t;
+typedef const bf16x8 __attribute__((address_space(3))) * lds8_t;
+__device__ __forceinline__ bf16x8 row_frag(ldsp_t lds, int row0, int st, int lane) {
+  return *(lds8_t)(lds + toff(row0 + (lane & 31), 2 * st + (lane >> 5)));
+}
+__device__ __forceinline__ bf16x8 tr_frag(ldsp_t lds, int r0, int s, int c0, int lane) {
+  const int h = lane >> 5, g2 = (lane >> 4) & 1, i16 = lane & 15, q = i16 >> 2, p = i16 & 3;
+  const int row = r0 + 16 * s + 4 * h + q;
+  const int col = c0 + 16 * g2 + 4 * p;
+  const ldsp_t a0 = lds + toff(row, col >> 3) + (col & 7);
+  const ldsp_t a1 = lds + toff(row + 8, col >> 3) + (col & 7);
+  short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)a0);
+  short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)a1);
+  typedef short short8_t __attribute__((ext_vector_type(8)));
+  short8_t s8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, s8);
+}
+// the tile's padding bitmask, formed HERE: called ahead of the next tile's DMA, so that the wait
+// for the mask bytes (which the compiler writes as vmcnt(0)) does not drain that DMA
+__device__ __forceinline__ unsigned long long pad_bits_now(const unsigned char* pad, int k0, int S, int lane) {
+  const unsigned long long pm = pad_bits(pad, k0, S, lane);
+  asm volatile("" ::"s"(pm));
+  return pm;
+}
+// HD-wide accumulator (scaled by a) -> the bf16 row of this lane, columns c0 .. c0 + 255; zeros if !keep
+__device__ __forceinline__ void store_row(bf16_t* row, const floatx16 (&x)[NDT], float a, bool keep, int hh) {
+#pragma unroll
+  for (int d = 0; d < NDT; ++d)
+#pragma unroll
+    for (int g = 0; g < 4; g += 2) {
+      uint2 wa = make_uint2(0u, 0u), wb = make_uint2(0u, 0u);
+      if (keep) {
+        wa.x = pack2bf(x[d][4 * g + 0] * a, x[d][4 * g + 1] * a);
+        wa.y = pack2bf(x[d][4 * g + 2] * a, x[d][4 * g + 3] * a);
+        wb.x = pack2bf(x[d][4 * g + 4] * a, x[d][4 * g + 5] * a);
+        wb.y = pack2bf(x[d][4 * g + 6] * a, x[d][4 * g + 7] * a);
+      }
+      store_pair16(row + d * 32, g, hh, wa, wb);
+    }
+}
+
+// Forward: workgroup = 128 queries (4 waves x 32, query on the lane), sweeping 64-key tiles in
+// plain order: S^T = K Q^T (32 MFMAs), the softmax update, O^T += V^T P^T (32 MFMAs).
+__global__ __launch_bounds__(256, 1) void attn256_fwd_kernel(AttnArgs p) {
+  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * PAIR];  // [slot][K|V]
+  const int S = p.S, H = p.H;
+  const int nqb = (S + QB - 1) / QB;
+  int bh, bi;
+  xcd_work(nqb, bh, bi);
+  const int qb = nqb - 1 - bi;  // heaviest causal blocks of a head first
+  const int n = bh / H, h = bh % H;
+  const int lane = threadIdx.x & 63, hh = lane >> 5;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int q0 = qb * QB + wid * 32;
+  const int q = q0 + (lane & 31);
+  const long long tok0 = (long long)n * S;
+  const bf16_t* Q = static_cast<const bf16_t*>(p.q) + h * HD;
+  const bf16_t* K = static_cast<const bf16_t*>(p.k) + tok0 * p.ld_qkv + h * HD;
+  const bf16_t* V = static_cast<const bf16_t*>(p.v) + tok0 * p.ld_qkv + h * HD;
+
+  bf16x8 qf[NST];
+#pragma unroll
+  for (int st = 0; st < NST; ++st)
+    qf[st] = q < S ? load_row8(Q + (tok0 + q) * p.ld_qkv + 16 * st + 8 * hh) : bf16x8{};
+  pin_loaded(qf);
+  const float c = p.scale * LOG2E;
+  const int kend = p.causal ? min(S, qb * QB + QB) : S;
+  const int ntiles = (kend + KT - 1) / KT;
+  // this wave's last tile holding a key it may attend to
+  const int last_w = p.causal ? min(ntiles - 1, max(0, min(q0 + 31, S - 1)) / KT) : ntiles - 1;
+  const unsigned char* pad = p.pad ? p.pad + (long long)n * S : nullptr;
+
+  int dv[NPW];
+  dma_voff(dv, p.ld_qkv, wid, lane);
+  auto issue = [&](int t) {
+    bf16_t* st = smem + (t & 1) * PAIR;
+    tile_dma(K, p.ld_qkv, t * KT, S, true, dv, st, wid);
+    tile_dma(V, p.ld_qkv, t * KT, S, true, dv, st + TILE, wid);
+  };
+
+  float m = -INFINITY, l = 0.f;
+  floatx16 o[NDT];
+#pragma unroll
+  for (int d = 0; d < NDT; ++d) zero16(o[d]);
+
+  issue(0);
+  for (int t = 0; t < ntiles; ++t) {
+    vm_wait<0>();    // this wave's pieces of tile t landed
+    ring_barrier();  // ... every wave's; and every wave is done with tile t-1's slot
+    const int kt0 = t * KT;
+    const unsigned long long pm = pad_bits_now(pad, kt0, S, lane);
+    if (t + 1 < ntiles) issue(t + 1);
+    if (t > last_w) continue;  // wave-uniform
+    const ldsp_t lk = (ldsp_t)smem + (t & 1) * PAIR;
+    const ldsp_t lv = lk + TILE;
+    floatx16 sc[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      zero16(sc[kb]);
+#pragma unroll
+      for (int st = 0; st < NST; ++st) sc[kb] = MFMA32(row_frag(lk, kb * 32, st, lane), qf[st], sc[kb]);
+      __builtin_amdgcn_sched_barrier(0);  // (register budget: the next block's 16 LDS reads stay below)
+    }
+    // Scores stay raw (unscaled) until the exponent: p = 2^(s*c - m) is one FMA + v_exp.
+    const bool need_mask = (p.causal && kt0 + KT - 1 > q0) || (kt0 + KT > S) || pad;  // wave-uniform
+    if (need_mask) {
+      // key kb*32 + (r&3) + 8(r>>2) + 4 hh of the tile is masked if it is > lim (causal / past
+      // the end) or padded: 32-bit compares of compile-time key offsets
+      const int limh = (p.causal ? min(q, S - 1) : S - 1) - kt0 - 4 * hh;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {
+        const unsigned pk = (unsigned)(pm >> (32 * kb)) >> (4 * hh);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kc = (r & 3) + 8 * (r >> 2);
+          if (kb * 32 + kc > limh || ((pk >> kc) & 1u)) sc[kb][r] = -INFINITY;
+        }
+      }
+    }
+    float mq[4];
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const floatx16& sq = sc[q4 >> 1];
+      const int r0 = (q4 & 1) * 8;
+      float v = max3f(sq[r0], sq[r0 + 1], sq[r0 + 2]);
+      v = max3f(v, sq[r0 + 3], sq[r0 + 4]);
+      v = max3f(v, sq[r0 + 5], sq[r0 + 6]);
+      mq[q4] = fmaxf(v, sq[r0 + 7]);
+    }
+    float mx = fmaxf(max3f(mq[0], mq[1], mq[2]), mq[3]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * c;  // scaled log2 units (c > 0)
+    // lazy rescale: the running max only moves when the tile max exceeds it by > 2^8, so
+    // p <= 256 (exact enough in f32 / bf16) and the O rescale is skipped on most tiles
+    if (__ballot(mx > m + 8.f)) {
+      const float mn = fmaxf(m, mx);
+      const float alpha = (mn == -INFINITY) ? 1.f : fast_exp2(m - mn);
+      m = mn;
+      l *= alpha;
+#pragma unroll
+      for (int d = 0; d < NDT; ++d) scale16(o[d], alpha);
+    }
+    const float nmu = (m == -INFINITY) ? 0.f : -m;
+    float lq[4] = {0.f, 0.f, 0.f, 0.f};  // (four independent partial row sums)
+    bf16x8 pb[2][2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = fast_exp2(fmaf(sc[kb][r], c, nmu));
+        sc[kb][r] = e;
+        lq[r & 3] += e;
+      }
+      pb[kb][0] = acc_frag(sc[kb], 0);
+      pb[kb][1] = acc_frag(sc[kb], 1);
+    }
+    l += (lq[0] + lq[1]) + (lq[2] + lq[3]);
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int ss = 0; ss < 2; ++ss) {
+#pragma unroll
+        for (int d = 0; d < NDT; ++d) o[d] = MFMA32(tr_frag(lv, kb * 32, ss, d * 32, lane), pb[kb][ss], o[d]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  }
+
+  l += __shfl_xor(l, 32, 64);  // the two lane halves summed different key rows
+  if (q < S) {
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    store_row(static_cast<bf16_t*>(p.o) + (tok0 + q) * p.ld_o + h * HD, o, inv, true, hh);
+    if (hh == 0) p.lse[(long long)bh * S + q] = (l > 0.f) ? (m + log2f(l)) / LOG2E : INFINITY;
+  }
+}
+
+// dQ (and the delta / log2-unit lse rows that the dK / dV kernel streams): attn_bwd_dq_kernel's
+// math -- per 32-key sub-block S^T, dP^T (32 MFMAs), dS^T, dQ^T += K^T dS^T (16 MFMAs) -- on the
+// 2-slot ring.
+__global__ __launch_bounds__(256, 1) void attn256_bwd_dq_kernel(AttnArgs p) {
+  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * PAIR];  // [slot][K|V]
+  const int S = p.S, H = p.H;
+  const int nqb = (S + QB - 1) / QB;
+  int bh, bi;
+  if (p.order == 1) work_order1(nqb, bh, bi);
+  else xcd_work(nqb, bh, bi);
+  const int qb = nqb - 1 - bi;
+  const int n = bh / H, h = bh % H;
+  const int lane = threadIdx.x & 63, hh = lane >> 5;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int q0 = qb * QB + wid * 32;
+  const int q = q0 + (lane & 31);
+  const long long tok0 = (long long)n * S;
+  const bf16_t* Q = static_cast<const bf16_t*>(p.q) + h * HD;
+  const bf16_t* K = static_cast<const bf16_t*>(p.k) + tok0 * p.ld_qkv + h * HD;
+  const bf16_t* V = static_cast<const bf16_t*>(p.v) + tok0 * p.ld_qkv + h * HD;
+  const bf16_t* dO = static_cast<const bf16_t*>(p.dout) + h * HD;
+  const bf16_t* Op = static_cast<const bf16_t*>(p.o) + h * HD;
+  const unsigned char* pad = p.pad ? p.pad + (long long)n * S : nullptr;
+
+  bf16x8 qf[NST], df[NST];
+  float acc = 0.f;
+#pragma unroll
+  for (int st = 0; st < NST; ++st) {
+    qf[st] = q < S ? load_row8(Q + (tok0 + q) * p.ld_qkv + 16 * st + 8 * hh) : bf16x8{};
+    df[st] = q < S ? load_row8(dO + (tok0 + q) * p.ld_o + 16 * st + 8 * hh) : bf16x8{};
+    const bf16x8 of = q < S ? load_row8(Op + (tok0 + q) * p.ld_o + 16 * st + 8 * hh) : bf16x8{};
+    float fo[8], fd[8];
+    unpack8(__builtin_bit_cast(uint4, of), fo);
+    unpack8(__builtin_bit_cast(uint4, df[st]), fd);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc = fmaf(fo[i], fd[i], acc);
+  }
+  const float c = p.scale * LOG2E;
+  const float dl = acc + __shfl_xor(acc, 32, 64);  // (the row's other half on lane ^ 32)
+  // (+inf stays +inf: a fully masked row)
+  const float lse2 = q < S ? p.lse[(long long)bh * S + q] * LOG2E : INFINITY;
+  // delta is stored NEGATED and the lse in log2 units, as attn_bwd_dq_kernel stores them
+  if (q < S && hh == 0) {
+    p.delta[(long long)bh * S + q] = -dl;
+    p.delta[(long long)p.N * H * S + (long long)bh * S + q] = lse2;
+  }
+  pin_loaded(qf);
+  pin_loaded(df);
+  pin_loaded(lse2);
+  pin_loaded(dl);
+  floatx16 dqt[NDT];
+#pragma unroll
+  for (int d = 0; d < NDT; ++d) zero16(dqt[d]);
+
+  const int kend = p.causal ? min(S, qb * QB + QB) : S;
+  const int ntiles = (kend + KT - 1) / KT;
+  int dv[NPW];
+  dma_voff(dv, p.ld_qkv, wid, lane);
+  auto issue = [&](int t) {
+    bf16_t* st = smem + (t & 1) * PAIR;
+    tile_dma(K, p.ld_qkv, t * KT, S, true, dv, st, wid);
+    tile_dma(V, p.ld_qkv, t * KT, S, true, dv, st + TILE, wid);
+  };
+
+  issue(0);
+  for (int t = 0; t < ntiles; ++t) {
+    vm_wait<0>();    // this wave's pieces of tile t landed
+    ring_barrier();  // ... every wave's; and every wave is done with tile t-1's slot
+    const int kt0 = t * KT;
+    const unsigned long long pm = pad_bits_now(pad, kt0, S, lane);
+    if (t + 1 < ntiles) issue(t + 1);
+    const ldsp_t lk = (ldsp_t)smem + (t & 1) * PAIR;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const int ks0 = kt0 + 32 * hf;
+      if (p.causal && ks0 > q0 + 31) continue;  // wave-uniform: no key <= any query
+      const bool need_mask = (p.causal && ks0 + 31 > q0) || (ks0 + 32 > S) || pad;  // wave-uniform
+      // S^T = K Q^T, dP^T - delta = V dO^T - delta (the dP accumulator starts at -delta of this lane's query)
+      floatx16 sa, dp;
+      zero16(sa);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] = -dl;
+#pragma unroll
+      for (int st = 0; st < NST; ++st) {
+        sa = MFMA32(row_frag(lk, 32 * hf, st, lane), qf[st], sa);
+        dp = MFMA32(row_frag(lk + TILE, 32 * hf, st, lane), df[st], dp);
+        if (st % 8 == 7) __builtin_amdgcn_sched_barrier(0);  // (register budget: 16 LDS reads at a time)
+      }
+      if (need_mask) {
+        const int limh = (p.causal ? min(q, S - 1) : S - 1) - ks0 - 4 * hh;
+        const unsigned pk = (unsigned)(pm >> (32 * hf)) >> (4 * hh);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kc = (r & 3) + 8 * (r >> 2);  // the element's key is ks0 + kc + 4 hh
+          float pv = fast_exp2(fmaf(sa[r], c, -lse2));
+          pv = (kc > limh || ((pk >> kc) & 1u)) ? 0.f : pv;
+          dp[r] = pv * dp[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dp[r] = fast_exp2(fmaf(sa[r], c, -lse2)) * dp[r];
+      }
+#pragma unroll
+      for (int ss = 0; ss < 2; ++ss) {
+        const bf16x8 db = acc_frag(dp, ss);
+#pragma unroll
+        for (int d = 0; d < NDT; ++d) dqt[d] = MFMA32(tr_frag(lk, 32 * hf, ss, d * 32, lane), db, dqt[d]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+  if (q < S)
+    store_row(static_cast<bf16_t*>(p.dq) + (tok0 + q) * p.ld_dqkv + h * HD, dqt, p.scale, true, hh);
+}
+
+// dK, dV (launched after the dQ kernel): workgroup = 128 keys (4 waves x 32, key on the lane; K and
+// V rows in registers), sweeping the 64-query tiles at or after the first key twice as ONE DMA
+// stream of 2 x count Q|dO pairs.  Pass 0: S = Q K^T (16 MFMAs per 32-query sub-block), P,
+// dV^T += dO^T P (16).  Pass 1: S, dP = dO V^T (32), P, dS = P (dP - delta), dK^T += Q^T dS (16).
+// Each pass ends with its store; dK and dV of a padded key are selected zeros.
+__global__ __launch_bounds__(256, 1) void attn256_bwd_dkdv_kernel(AttnArgs p) {
+  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * PAIR];     // [slot][Q|dO]
+  __shared__ __attribute__((aligned(16))) float srow[2][2][KT];      // [slot][lse|delta]
+  const int S = p.S, H = p.H;
+  const int nkb = (S + QB - 1) / QB;
+  int bh, kb;
+  if (p.order == 1) work_order1(nkb, bh, kb);
+  else xcd_work(nkb, bh, kb);  // kb = 0 (the most queries under the causal mask) first
+  const int n = bh / H, h = bh % H;
+  const int lane = threadIdx.x & 63, hh = lane >> 5;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int k0 = kb * QB + wid * 32;
+  const int key = k0 + (lane & 31);
+  const long long tok0 = (long long)n * S;
+  const bf16_t* Q = static_cast<const bf16_t*>(p.q) + tok0 * p.ld_qkv + h * HD;
+  const bf16_t* K = static_cast<const bf16_t*>(p.k) + tok0 * p.ld_qkv + h * HD;
+  const bf16_t* V = static_cast<const bf16_t*>(p.v) + tok0 * p.ld_qkv + h * HD;
+  const bf16_t* dO = static_cast<const bf16_t*>(p.dout) + tok0 * p.ld_o + h * HD;
+  const float* lse = p.delta + (long long)p.N * H * S + (long long)bh * S;  // log2 units
+  const float* delta = p.delta + (long long)bh * S;                         // negated
+  const bool key_ok = key < S && !(p.pad && p.pad[(long long)n * S + min(key, S - 1)]);
+  const float c = p.scale * LOG2E;
+
+  const int qt_begin = p.causal ? (kb * QB) / KT : 0;
+  const int count = (S + KT - 1) / KT - qt_begin;  // >= 1: the block's first key is < S
+
+  int vq[NPW], vd[NPW];
+  dma_voff(vq, p.ld_qkv, wid, lane);
+  dma_voff(vd, p.ld_o, wid, lane);
+  auto issue = [&](int e) {  // stream element e: query tile e of pass 0, or e - count of pass 1
+    const int slot = e & 1, qt = qt_begin + (e >= count ? e - count : e);
+    bf16_t* st = smem + slot * PAIR;
+    tile_dma(Q, p.ld_qkv, qt * KT, S, true, vq, st, wid);
+    tile_dma(dO, p.ld_o, qt * KT, S, true, vd, st + TILE, wid);
+    if (wid == 0) {
+      dma4(rows_rsrc(lse, 4, qt * KT, S, true), lane * 4, &srow[slot][0][0]);
+      dma4(rows_rsrc(delta, 4, qt * KT, S, true), lane * 4, &srow[slot][1][0]);
+    }
+  };
+
+  // the workgroup's 128 K rows land in slot 0 and its V rows in slot 1 as tile images; the
+  // lanes read their row fragments from there, and only then does the stream start
+  bf16x8 kf[NST], vf[NST];
+  tile_dma(K, p.ld_qkv, kb * QB, S, true, vq, smem, wid);
+  tile_dma(K, p.ld_qkv, kb * QB + KT, S, true, vq, smem + TILE, wid);
+  tile_dma(V, p.ld_qkv, kb * QB, S, true, vq, smem + PAIR, wid);
+  tile_dma(V, p.ld_qkv, kb * QB + KT, S, true, vq, smem + PAIR + TILE, wid);
+  vm_wait<0>();
+  ring_barrier();
+#pragma unroll
+  for (int st = 0; st < NST; ++st) {
+    kf[st] = row_frag((ldsp_t)smem + (wid >> 1) * TILE, 32 * (wid & 1), st, lane);
+    vf[st] = row_frag((ldsp_t)smem + PAIR + (wid >> 1) * TILE, 32 * (wid & 1), st, lane);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every wave done with the two slots
+  __builtin_amdgcn_sched_barrier(0);
+  ring_barrier();
+  issue(0);
+
+  floatx16 acc[NDT];  // dV^T in pass 0, dK^T in pass 1
+  sfor<2>([&](auto PASS_) {
+    constexpr int PASS = decltype(PASS_)::value;
+#pragma unroll
+    for (int d = 0; d < NDT; ++d) zero16(acc[d]);
+    for (int i = 0; i < count; ++i) {
+      const int e = PASS * count + i;
+      vm_wait<0>();    // this wave's pieces of element e landed
+      ring_barrier();  // ... every wave's; and every wave is done with element e-1's slot
+      if (e + 1 < 2 * count) issue(e + 1);
+      const int slot = e & 1;
+      const ldsp_t lq = (ldsp_t)smem + slot * PAIR;
+      const ldsp_t ldo = lq + TILE;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int qs0 = (qt_begin + i) * KT + 32 * hf;
+        if (p.causal && qs0 + 31 < k0) continue;          // wave-uniform: no query >= any key
+        const bool diag = p.causal && qs0 < k0 + 31;      // wave-uniform: some key > some query
+        // S = Q K^T; pass 1: dP - delta = dO V^T - delta (the accumulator starts at the buffer's -delta)
+        floatx16 sa, dp;
+        zero16(sa);
+        if constexpr (PASS == 1) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const float4 d4 = *reinterpret_cast<const float4*>(&srow[slot][1][32 * hf + 8 * g + 4 * hh]);
+            dp[4 * g + 0] = d4.x;
+            dp[4 * g + 1] = d4.y;
+            dp[4 * g + 2] = d4.z;
+            dp[4 * g + 3] = d4.w;
+          }
+        }
+#pragma unroll
+        for (int st = 0; st < NST; ++st) {
+          sa = MFMA32(row_frag(lq, 32 * hf, st, lane), kf[st], sa);
+          if constexpr (PASS == 1) dp = MFMA32(row_frag(ldo, 32 * hf, st, lane), vf[st], dp);
+        }
+        // P; element (g, e) holds query qs0 + 8 g + 4 hh + e
+        sfor<4>([&](auto G) {
+          constexpr int g = decltype(G)::value;
+          const float4 l4 = *reinterpret_cast<const float4*>(&srow[slot][0][32 * hf + 8 * g + 4 * hh]);
+          const float lv[4] = {l4.x, l4.y, l4.z, l4.w};
+#pragma unroll
+          for (int x = 0; x < 4; ++x) sa[4 * g + x] = fast_exp2(fmaf(sa[4 * g + x], c, -lv[x]));
+        });
+        if (diag) {
+          // masked when key - qs0 - 4 hh > 8 g + e (a padded key's P only reaches this lane's own
+          // dK / dV column: zeroed at the store)
+          const int kd = key - qs0 - 4 * hh;
+          sfor<16>([&](auto R) {
+            constexpr int r = decltype(R)::value;
+            zero_if_gt<8 * (r >> 2) + (r & 3)>(sa, r, kd);
+          });
+        }
+        if constexpr (PASS == 1) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sa[r] = sa[r] * dp[r];  // dS
+        }
+        const ldsp_t lt = PASS == 0 ? ldo : lq;  // dV^T += dO^T P, dK^T += Q^T dS
+#pragma unroll
+        for (int ss = 0; ss < 2; ++ss) {
+          const bf16x8 b = acc_frag(sa, ss);
+#pragma unroll
+          for (int d = 0; d < NDT; ++d) acc[d] = MFMA32(tr_frag(lt, 32 * hf, ss, d * 32, lane), b, acc[d]);
+        }
+      }
+    }
+    if (key < S) {
+      bf16_t* out = static_cast<bf16_t*>(PASS == 0 ? p.dv : p.dk) + (tok0 + key) * p.ld_dqkv + h * HD;
+      store_row(out, acc, PASS == 0 ? 1.f : p.scale, key_ok, hh);
+    }
+  });
+}
+}  // namespace hd256
+
 // ------------------------------------------------------------------ launchers
 // Which kernel runs, and at how many workgroups per CU (all measured on MI355X, GPT-2 small shape
 // N = 64, H = 12 unless noted; bench/attn_time.py, bench/attn_one.py):
@@ -1430,7 +1925,8 @@ static int launch_fwd(const AttnArgs* a, hipStream_t stream) {
   const dim3 blocks((unsigned)(nqb * a->N * a->H));  // one workgroup per 128-query block (xcd_work() maps it)
   const int nitems = ((nqb + 1) / 2) * a->N * a->H;  // pair stream: one workgroup per pair of blocks
   const dim3 pairs((unsigned)nitems);
-  if (a->hd == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, 1>), blocks, dim3(256), 0, stream, *a);
+  if (a->hd == 256) hipLaunchKernelGGL(hd256::attn256_fwd_kernel, blocks, dim3(256), 0, stream, *a);
+  else if (a->hd == 128) hipLaunchKernelGGL((attn_fwd_kernel<128, 1>), blocks, dim3(256), 0, stream, *a);
   else if (a->hd == 64) hipLaunchKernelGGL((attn_fwd3_kernel<64, 2>), pairs, dim3(256), 0, stream, *a, nitems);
   else if (a->S < 512) hipLaunchKernelGGL((attn_fwd2_kernel<32, 2>), pairs, dim3(256), 0, stream, *a, nitems);
   else hipLaunchKernelGGL((attn_fwd3_kernel<32, 2>), pairs, dim3(256), 0, stream, *a, nitems);
@@ -1444,7 +1940,10 @@ static void launch_bwd_at(const AttnArgs* a, dim3 blocks, hipStream_t stream) {
 }
 static int launch_bwd(const AttnArgs* a, hipStream_t stream) {
   const dim3 blocks((unsigned)(((a->S + QB - 1) / QB) * a->N * a->H));  // one workgroup per 128 rows
-  if (a->hd == 128) launch_bwd_at<128, 1>(a, blocks, stream);
+  if (a->hd == 256) {
+    hipLaunchKernelGGL(hd256::attn256_bwd_dq_kernel, blocks, dim3(256), 0, stream, *a);
+    hipLaunchKernelGGL(hd256::attn256_bwd_dkdv_kernel, blocks, dim3(256), 0, stream, *a);
+  } else if (a->hd == 128) launch_bwd_at<128, 1>(a, blocks, stream);
   else if (a->hd == 64) launch_bwd_at<64, 2>(a, blocks, stream);
   else launch_bwd_at<32, 3>(a, blocks, stream);
   return (int)hipGetLastError();
@@ -1454,9 +1953,9 @@ static int launch_bwd(const AttnArgs* a, hipStream_t stream) {
 
 using namespace dpc;
 
-// Host-side checks: the kernels assume 16-B aligned rows (ld % 8 == 0) and head_dim 32 / 64 / 128.
+// Host-side checks: the kernels assume 16-B aligned rows (ld % 8 == 0) and head_dim 32 / 64 / 128 / 256.
 static bool attn_args_ok(const AttnArgs* a, bool bwd) {
-  if (a->hd != 32 && a->hd != 64 && a->hd != 128) return false;
+  if (a->hd != 32 && a->hd != 64 && a->hd != 128 && a->hd != 256) return false;
   if (a->N <= 0 || a->S <= 0 || a->H <= 0) return false;
   if (a->ld_qkv % 8 || a->ld_o % 8 || (bwd && a->ld_dqkv % 8)) return false;
   // (rows_rsrc's 32-bit offsets: one sequence's rows of Q / K / V / O / dO span < 4 GiB)
